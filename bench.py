@@ -3,9 +3,16 @@
 Gset-G22-sized graph with 2^16 parallel envs per GPU, next-state emitted into a rollout ring
 (the PPO `obs[t+1] = next_obs` pattern), 1-byte spins in and out.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline needs: set-up, W warm-up steps, ONE timed region of exactly K steps, the outputs
+(`--dump-outputs`) and the JSON line.  Everything else -- the CPU baselines, the exchange probe, config #5's shard, the
+nontemporal-store repeat, the BASELINE configs block, the end-of-run parity check and the N > 1 shard-cover check -- runs
+only with `--full`.  `--dump-outputs DIR` writes what the last timed step computed (next state, reward, obj: a fixed, seeded
+sample of envs, at most 48 MB) as DIR/<name>.npy; the inputs depend only on the arguments, so two builds compare output for
+output.
 
 `python bench.py --gpus N` with N > 1 and no torchrun environment starts the N ranks itself (a fresh
 `python -m torch.distributed.run` child, started before this process touches the GPU), relays rank 0's JSON line
@@ -18,13 +25,13 @@ HBM bytes per env-step = 2N + 20.  Envs are sharded over 
 data-path collective (weak scaling: 2^16 envs per GPU); the episode-boundary best-objective
 exchange (8-byte RCCL all-reduce) runs once at the end of every timed region when N > 1.
 
-Timing: W warm-up steps, then R (`--repeats`, default 5) timed regions of EXACTLY K steps each, every region
+Timing: W warm-up steps, then R (`--repeats`, default 1) timed regions of EXACTLY K steps each, every region
 bracketed by barrier + synchronize on both sides; a rank's time runs from the release of the opening barrier to its own
 synchronize after the last step and the exchange, and the region counts as the MAX over ranks (the closing barrier
 itself -- a second collective latency that no step waits for -- is not inside any rank's interval).  The line reports
 the MEDIAN region (`ms_per_step`, `value`) and all of them (`ms_per_step_all`).
 
-Rank 0 prints ONE JSON line.  `roofline` is measured live with HIP events on the launch stream;
+Rank 0 prints ONE JSON line.  `roofline` is measured live with HIP events on the launch stream; with `--full`,
 `cpu_baseline` is the C oracle (reference algorithm: flip + full objective re-evaluation, OpenMP)
 timed on the host cores on a bounded sample (rank 0, N = 1 only); `cpu_baseline_ref_shaped` is the reference's
 own op chain in torch-CPU ops (oracle/oracle_torch.py).  `config5_shard` is BASELINE config #5's per-GPU shard
@@ -59,7 +66,14 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps each; the median is reported")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps each; the median is reported (default 1; --full's secondary "
+                         "measurements: 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beyond the headline (CPU baselines, exchange probe, config #5, "
+                         "hbm_only, the configs block, the parity and shard-cover checks); the --no-* options below prune it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--envs-per-gpu", type=int, default=1 << 16)
     ap.add_argument("--gset", type=int, default=22, help="Gset id whose (n, m) the graph has (22 = headline)")
     ap.add_argument("--slots", type=int, default=8, help="rollout ring depth (slots of B*N bytes)")
@@ -569,11 +583,13 @@ def dry_run(a):
 # --------------------------------------------------------------------------- #
 # the timed workload
 # --------------------------------------------------------------------------- #
-def measure(a, gset, B, steps, warmup, repeats, dev, rank, local_rank, world, via_env=False, verify=True, env_offset=None):
+def measure(a, gset, B, steps, warmup, repeats, dev, rank, local_rank, world, via_env=False, verify=True, env_offset=None,
+            outputs=False):
     """W warm-up steps, then `repeats` regions of exactly `steps` K4 launches.  Returns a dict with the per-region
     wall times (MAX over ranks), the HIP-event kernel times of this rank and -- N > 1 -- every rank's own kernel / exchange /
     region times (what an N > 1 line needs to attribute a shortfall: slow kernels on one rank, the exchange, or skew).
-    `env_offset`: global id of this rank's env 0 (default rank * B: weak scaling, equal shards)."""
+    `env_offset`: global id of this rank's env 0 (default rank * B: weak scaling, equal shards).
+    `outputs`: also return, under "outputs", host copies of what the last timed step computed (dump_outputs)."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -598,6 +614,7 @@ def measure(a, gset, B, steps, warmup, repeats, dev, rank, local_rank, world, vi
     # one pre-validated launcher per (slot, action vector) pair of the cycle: the timed loop is then a
     # bare C-ABI call per step (the ring and the action pool are fixed buffers)
     period = S * A // math.gcd(S, A)
+    last = {}           # via_env: what the class returned from the latest step
     if via_env:
         import types
         from rlsolver_amd.envs.env_PPO import EnvMaxcut as EnvMaxcutGym
@@ -606,7 +623,7 @@ def measure(a, gset, B, steps, warmup, repeats, dev, rank, local_rank, world, vi
         env._xs, env._obj = slots[0], obj       # same initial state as the launcher mode (env._xs: no resync needed, obj IS its cut)
 
         def step(t):
-            env.step(actions[t % A], out=slots[(t + 1) % S])
+            _, last["reward"], last["done"], last["cur"] = env.step(actions[t % A], out=slots[(t + 1) % S])
     else:
         launchers = [ops.maxcut_step_launcher(g, slots[t % S], slots[(t + 1) % S], actions[t % A], obj, reward)
                      for t in range(period)]
@@ -614,8 +631,12 @@ def measure(a, gset, B, steps, warmup, repeats, dev, rank, local_rank, world, vi
         def step(t):
             launchers[t % period]()
 
+    # (graph mode needs at least one eager warm-up launch: a kernel's first launch loads its code object, which a capture must not do)
+    use_graph = (not via_env) and (a.graph == "on" or (a.graph == "auto" and steps <= 100 and warmup > 0))
+    # graph mode: one eager step, the captures, then the rest of the warm-up -- the timed region starts on a busy GPU, not after
+    # the idle of the captures
     t = 0
-    for _ in range(warmup):
+    for _ in range(min(warmup, 1) if use_graph else warmup):
         step(t)
         t += 1
 
@@ -627,14 +648,13 @@ def measure(a, gset, B, steps, warmup, repeats, dev, rank, local_rank, world, vi
     if use_pg:   # the first collective builds the communicator (16 ms on a 1-rank RCCL group): not part of any region, and
         ex.exchange(obj)          # not something a capture may do
         torch.cuda.synchronize(dev)
-    # (auto needs at least one eager warm-up launch: a kernel's first launch loads its code object, which a capture must not do)
-    use_graph = (not via_env) and (a.graph == "on" or (a.graph == "auto" and steps <= 100 and warmup > 0))
     graphs = []
     if use_graph:
         # one hipGraph per timed region: region r runs steps t_r .. t_r + steps - 1 of the ring / action cycle (capture enqueues
-        # nothing: the launchers resolve torch's current stream at every call, which is the capture stream here)
+        # nothing: the launchers resolve torch's current stream at every call, which is the capture stream here); the regions
+        # follow the whole warm-up, steps 0 .. warmup - 1
         def capture(with_exchange):
-            out, tc = [], t
+            out, tc = [], warmup
             torch.cuda.synchronize(dev)
             for _ in range(repeats):
                 gr = torch.cuda.CUDAGraph()
@@ -668,6 +688,17 @@ def measure(a, gset, B, steps, warmup, repeats, dev, rank, local_rank, world, vi
                 torch.cuda.synchronize(dev)
     else:
         exch_in_graph = False
+    if use_graph and t < warmup:
+        # the rest of the warm-up as a graph of its own: the process's first graph replay happens here, not in a timed region
+        gw = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gw):
+            for k in range(t, warmup):
+                step(k)
+        gw.replay()
+        t = warmup
+    while t < warmup:
+        step(t)
+        t += 1
 
     def barrier():
         if use_pg:
@@ -753,6 +784,20 @@ def measure(a, gset, B, steps, warmup, repeats, dev, rank, local_rank, world, vi
 
     res = {"wall": wall, "kernel_s": kern, "exchange_s": exch, "per_rank": per_rank, "N": N, "E": len(mygraph), "is_real": is_real,
            "B": B, "graph": use_graph, "graph_arr": np.asarray(mygraph, dtype=np.int64)}
+    if outputs:
+        # what a caller of the timed path holds after the last step t - 1: the next state it emitted (slot t % S), its reward
+        # and the running objective (the class path also returns done and cur).  The next state is B x N, so every array is
+        # the same fixed, seeded sample of envs, at most 48 MB in all
+        per_env = 4 * N + 4 + 8 + 8 + (8 if via_env else 0)       # next_state, reward, obj, env_ids (+ done, cur)
+        k = min(B, max(1, (48 << 20) // per_env))
+        rows = np.arange(B) if k == B else np.sort(np.random.RandomState(0).choice(B, size=k, replace=False))
+        idx = torch.from_numpy(rows).to(dev)
+        res["outputs"] = {"env_ids": (rows + env_offset).astype(np.float64),
+                          "next_state": slots[t % S].index_select(0, idx).float().cpu().numpy(),
+                          "reward": (last["reward"] if via_env else reward).index_select(0, idx).cpu().numpy(),
+                          "obj": obj.index_select(0, idx).double().cpu().numpy()}
+        if via_env:
+            res["outputs"].update(done=last["done"].index_select(0, idx).cpu().numpy(), cur=last["cur"].index_select(0, idx).cpu().numpy())
     return res          # the ring and the launchers die with this frame: the next workload gets the memory back
 
 
@@ -799,6 +844,15 @@ def summarize(res, steps, world, total_envs=None):
                          "algorithmic_bytes_per_launch": bytes_per_launch}}
 
 
+def dump_outputs(d, outs):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 / float64 as measure() made them."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, arr in outs.items():
+        assert arr.dtype in (np.float32, np.float64), (name, arr.dtype)
+        np.save(os.path.join(d, f"{name}.npy"), arr)
+
+
 def main():
     argv = sys.argv[1:]
     a = parse(argv)
@@ -812,7 +866,7 @@ def main():
     if a.exchange_probe:
         return exchange_probe_child(a)
     probe = None
-    if a.gpus == 1 and not a.no_exchange_probe and os.environ.get("RLS_FORCE_PG") != "1":
+    if a.full and a.gpus == 1 and not a.no_exchange_probe and os.environ.get("RLS_FORCE_PG") != "1":
         probe = exchange_probe_parent(a)        # a child process, started and finished before this one touches the GPU
 
     import torch
@@ -826,39 +880,43 @@ def main():
         local_rank = 0                                  # test mode: all ranks on the one GPU of the box
     dev = torch.device("cuda", local_rank)
     torch.cuda.set_device(dev)
-    R = max(1, a.repeats)
+    R = max(1, a.repeats or 1)
+    R2 = max(1, a.repeats or 5)         # config #5 and hbm_only (--full)
 
     strong = a.global_envs > 0
     G = a.global_envs if strong else world * a.envs_per_gpu
     env_offset, B_rank = rdist.env_shard(G, rank, world)          # weak: rank * envs_per_gpu, envs_per_gpu
+    verify = a.full and not a.no_verify
     res = measure(a, a.gset, B_rank, a.steps, a.warmup, R, dev, rank, local_rank, world,
-                  via_env=a.via_env, verify=not a.no_verify, env_offset=env_offset)
+                  via_env=a.via_env, verify=verify, env_offset=env_offset, outputs=a.dump_outputs is not None and rank == 0)
+    if "outputs" in res:
+        dump_outputs(a.dump_outputs, res.pop("outputs"))
     torch.cuda.empty_cache()
     res5 = None
     is_c5 = a.gset == 70 and (G == world * 131072)
-    if not a.no_config5 and not is_c5:
+    if a.full and not a.no_config5 and not is_c5:
         # BASELINE config #5's per-GPU shard, measured the same way (never mixed into `value`)
-        res5 = measure(a, 70, 131072, max(1, min(a.steps, 200)), min(a.warmup, 20), R, dev, rank, local_rank, world,
-                       verify=not a.no_verify)
+        res5 = measure(a, 70, 131072, max(1, min(a.steps, 200)), min(a.warmup, 20), R2, dev, rank, local_rank, world,
+                       verify=verify)
         torch.cuda.empty_cache()
     res_nts = None
-    if world == 1 and not a.no_hbm_only and res["B"] * res["N"] <= MALL_BYTES:
+    if a.full and world == 1 and not a.no_hbm_only and res["B"] * res["N"] <= MALL_BYTES:
         # the same loop with nontemporal stores: a ring slot of B*N bytes fits the 256 MB Infinity Cache, and with plain stores
         # (the launcher's choice at this size) the next step's reads hit what this step wrote -- FETCH_SIZE counts those hits.
         # With nontemporal stores nothing a step writes is kept for the next one to find: the HBM-only figure.
         from rlsolver_amd import _abi
         _abi.tuning_set("RLS_STEP_NTS", 1)
         try:
-            res_nts = measure(a, a.gset, B_rank, max(1, min(a.steps, 200)), min(a.warmup, 20), R, dev, rank, local_rank, world,
-                              verify=not a.no_verify, env_offset=env_offset)
+            res_nts = measure(a, a.gset, B_rank, max(1, min(a.steps, 200)), min(a.warmup, 20), R2, dev, rank, local_rank, world,
+                              verify=verify, env_offset=env_offset)
         finally:
             _abi.tuning_unset("RLS_STEP_NTS")
         torch.cuda.empty_cache()
     cfgs = None
-    if rank == 0 and world == 1 and not a.no_configs:
+    if a.full and rank == 0 and world == 1 and not a.no_configs:
         cfgs = extra_configs(dev)
     cover = None
-    if world > 1:
+    if a.full and world > 1:
         covs = [None] * world
         dist.all_gather_object(covs, shard_cover(G, rank, world))
         if rank == 0:
@@ -875,7 +933,8 @@ def main():
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": s["ms_per_step"],
             "repeats": R, "ms_per_step_all": s["ms_per_step_all"],
-            "timing": f"median of {R} regions of exactly {a.steps} steps, each bracketed by barrier + synchronize, MAX over ranks",
+            "timing": (f"median of {R} regions" if R > 1 else "one region") + f" of exactly {a.steps} steps, "
+                      + ("each " if R > 1 else "") + "bracketed by barrier + synchronize, MAX over ranks",
             "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
             # the graph: the real Gset file when data/gset/gset_<k>.txt is present, else the G(n, m) stand-in of its size; spins
             # and actions are drawn either way
@@ -932,7 +991,7 @@ def main():
             out["configs"] = cfgs
         if probe is not None:
             out["exchange_probe"] = probe
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(res["graph_arr"], N, a.cpu_seconds)
             out["cpu_baseline_ref_shaped"] = cpu_baseline_ref_shaped(res["graph_arr"], N, max(3.0, a.cpu_seconds / 2))
 

@@ -123,7 +123,7 @@ def test_bench_line_carries_the_exchange_probe():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "RLS_FORCE_PG"):
         e.pop(k, None)
     e["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--repeats", "3",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--repeats", "3",
                         "--envs-per-gpu", "4096", "--no-cpu-baseline", "--no-config5", "--no-configs"], env=e,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -146,7 +146,7 @@ def test_bench_two_ranks_sharing_the_gpu(launch):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "RLS_FORCE_PG"):
         e.pop(k, None)
     e["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    args = ["--gpus", "2", "--share-gpu", "--steps", "20", "--warmup", "5", "--repeats", "3", "--envs-per-gpu", "8192",
+    args = ["--gpus", "2", "--share-gpu", "--full", "--steps", "20", "--warmup", "5", "--repeats", "3", "--envs-per-gpu", "8192",
             "--no-cpu-baseline", "--no-config5"]
     if launch == "self-spawn":
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), *args]
@@ -174,7 +174,7 @@ def test_bench_eight_ranks_sharing_the_gpu_strong_scaling_line_explains_itself()
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "RLS_FORCE_PG"):
         e.pop(k, None)
     e["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--share-gpu", "--steps", "20", "--warmup", "5", "--repeats", "3",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--share-gpu", "--full", "--steps", "20", "--warmup", "5", "--repeats", "3",
            "--global-envs", "16384", "--no-cpu-baseline", "--no-config5"]
     p = subprocess.run(cmd, env=e, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1500, cwd=ROOT)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
