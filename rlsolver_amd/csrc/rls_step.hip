@@ -49,9 +49,21 @@ template <bool NT, typename V> __device__ __forceinline__ V ld_vec(const V* p) {
     if constexpr (NT) return __builtin_nontemporal_load(p);
     else return *p;
 }
-template <bool NT, typename V> __device__ __forceinline__ void st_vec(V* p, V v) {
-    if constexpr (NT) __builtin_nontemporal_store(v, p);
-    else *p = v;
+// store policies of the emitted run: plain | nontemporal | write-through (sc1: the line goes on to the Infinity Cache and is not
+// kept dirty in the XCD's L2).  A launch that leaves its output dirty in the L2s pays for writing it back at the kernel boundary;
+// write-through stores pay as they go (tools/ceilings/ring_copy.hip, K4's ring at G22 size: 35.2 us per pass plain, 31.6
+// write-through, 43.0 nontemporal -- that one also gives up the Infinity Cache)
+enum : int { kStPlain = 0, kStNt = 1, kStWt = 2 };
+template <int ST, typename V> __device__ __forceinline__ void st_vec(V* p, V v) {
+    if constexpr (ST == kStNt) {
+        __builtin_nontemporal_store(v, p);
+    } else if constexpr (ST == kStWt) {
+        static_assert(sizeof(V) == 16, "write-through stores are 16-byte vectors");
+        // (s_nop 1: the wait states a VALU write of the data registers needs after a 16-byte store; hipcc pads nothing in asm)
+        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(v) : "memory");
+    } else {
+        *p = v;
+    }
 }
 
 // s_waitcnt vmcnt(k) for a wave-uniform RUN-TIME k (the instruction takes an immediate): a scalar jump over 64 one-line cases
@@ -75,7 +87,7 @@ __device__ __forceinline__ void wait_vmcnt_le(int k) {
 #undef RLS_W
 }
 
-template <typename T, int EPW, int MODE, bool EMIT, bool VEC, bool WEIGHTED, bool NTL, bool NTS>
+template <typename T, int EPW, int MODE, bool EMIT, bool VEC, bool WEIGHTED, bool NTL, int ST>
 __global__ __launch_bounds__(256) void k_maxcut_step(const T* __restrict__ xin, T* __restrict__ xout,
                                                      int64_t B, int64_t N,
                                                      const int32_t* __restrict__ rowptr,
@@ -200,7 +212,7 @@ __global__ __launch_bounds__(256) void k_maxcut_step(const T* __restrict__ xin, 
 #pragma unroll
                 for (int k = 0; k < EPW; ++k)
                     if (i == fvec[k]) v = SpinVec<T>::flip_at(v, fidx[k]);
-                st_vec<NTS>(dst + i, v);
+                st_vec<ST>(dst + i, v);
             }
             tail_copy();
         } else if constexpr (MODE == 1) {
@@ -233,7 +245,7 @@ __global__ __launch_bounds__(256) void k_maxcut_step(const T* __restrict__ xin, 
 #pragma unroll
                         for (int k = 0; k < EPW; ++k)
                             if (i == fvec[k]) v = SpinVec<T>::flip_at(v, fidx[k]);
-                        st_vec<NTS>(dst + i, v);
+                        st_vec<ST>(dst + i, v);
                     }
                 }
             }
@@ -289,7 +301,7 @@ __global__ __launch_bounds__(256) void k_maxcut_step(const T* __restrict__ xin, 
 #pragma unroll
                     for (int k = 0; k < EPW; ++k)
                         if (i == fvec[k]) v = SpinVec<T>::flip_at(v, fidx[k]);
-                    st_vec<NTS>(dst + i, v);
+                    st_vec<ST>(dst + i, v);
                 }
             }
             tail_copy();                                                     // (a short last run only)
@@ -382,7 +394,7 @@ __global__ __launch_bounds__(256) void k_maxcut_step(const T* __restrict__ xin, 
 #pragma unroll 4
             for (int64_t slot0 = 0; slot0 < nvec + h_out; slot0 += kWave) {
                 const int64_t i = slot0 + lane - h_out;
-                if (i >= 0 && i < nvec) st_vec<NTS>(dst + i, stage_v[i]);
+                if (i >= 0 && i < nvec) st_vec<ST>(dst + i, stage_v[i]);
             }
             for (int64_t i = nvec * PER + lane; i < nel; i += kWave) xout[b0 * N + i] = stage[i];
         }
@@ -393,11 +405,12 @@ __global__ __launch_bounds__(256) void k_maxcut_step(const T* __restrict__ xin, 
 // tuning knobs (rls_tuning_set; no environment variable is read by the production library): nts = -1 automatic | 0 | 1
 // (nontemporal stores), epw / wpb = 0: automatic, persist = -1 automatic | 0 one run per wave | k: k workgroup rounds per CU
 // resident, waves loop; chase = -1 automatic | 0 MODE 2 (stores after the last load) | 1 MODE 3 (stores chase the loads);
-// align = 0: load / store instructions start where the run starts (before round 4's fix)
-struct StepKnobs { int nts, epw, wpb, persist, chase, align; };
+// align = 0: load / store instructions start where the run starts (before round 4's fix); wt = -1 automatic | 0 | 1 (write-through
+// stores where the stores are not nontemporal; staged forms only)
+struct StepKnobs { int nts, epw, wpb, persist, chase, align, wt; };
 static StepKnobs step_knobs() {
     return StepKnobs{(int)knob(KN_STEP_NTS, -1), (int)knob(KN_STEP_EPW, 0), (int)knob(KN_STEP_WPB, 0), (int)knob(KN_STEP_PERSIST, -1),
-                     (int)knob(KN_STEP_CHASE, -1), (int)knob(KN_STEP_ALIGN, 1)};
+                     (int)knob(KN_STEP_CHASE, -1), (int)knob(KN_STEP_ALIGN, 1), (int)knob(KN_STEP_WT, -1)};
 }
 
 }  // namespace rls
@@ -408,8 +421,9 @@ using namespace rls;
 //   emit, vectorisable runs   MODE 2: the run staged in LDS by LDS-DMA with nontemporal loads (every input byte is read once),
 //                             up to the whole 160 KB of a CU per workgroup (f32 rows of 10^4 nodes: 2 waves x 40 KB);
 //                             stores nontemporal when the batch is larger than the 256 MB Infinity Cache (nothing of it
-//                             can still be there when the next step reads it: +3 points at G70 size), plain otherwise
-//                             (the next step's reads hit what this step wrote: +6 points at G22 size)
+//                             can still be there when the next step reads it: +3 points at G70 size), write-through otherwise
+//                             (the next step's reads hit what this step wrote: +6 points at G22 size over nontemporal; and no
+//                             dirty L2 lines are left for the kernel boundary to write back: round 7, see st_vec)
 //   emit, rows too long       MODE 1 (register batches, gathers from global), nontemporal stores
 //   emit, odd row lengths     MODE 0 element-wise
 //   in place                  O(deg) bytes
@@ -467,31 +481,35 @@ extern "C" int rls_maxcut_step(const rls_graph* g, const void* x_in, void* x_out
     // 8 TB/s), 1-byte rows nothing (0.694 / 0.694, 0.738 / 0.739): their runs are 8 - 10 pieces, back before the first could leave
     const bool chase = staged && nch_run + 1 + epw <= 62 && (knobs.chase > 0 || (knobs.chase < 0 && spin_bytes == 4));   // (+ 1: a shifted run's extra piece)
     const bool nts = knobs.nts >= 0 ? knobs.nts != 0 : ((size_t)B * N * spin_bytes > ((size_t)256 << 20));
+    // write-through in place of plain stores: MODE 2 by default (measured: tools/ceilings/ring_copy.hip, bench.py); MODE 3 when forced
+    const bool wt = !nts && (knobs.wt > 0 || (knobs.wt < 0 && !chase));
 
-#define LAUNCH_STEP_E(T, EPW, MODE, EMIT, VEC, NTL, NTS)                                                       \
+#define LAUNCH_STEP_E(T, EPW, MODE, EMIT, VEC, NTL, ST)                                                        \
     do {                                                                                                       \
-        auto kern = k_maxcut_step<T, EPW, MODE, EMIT, VEC, false, NTL, NTS>;                                   \
+        auto kern = k_maxcut_step<T, EPW, MODE, EMIT, VEC, false, NTL, ST>;                                    \
         if (lds > 64 * 1024)                                                                                   \
             ensure_dyn_lds((const void*)kern, lds); \
         hipLaunchKernelGGL(kern, grid, block, lds, s, (const T*)x_in, (T*)x_out, B, N, g->rowptr, g->col, g->wgt, \
                            action, obj, reward, cur, done, done_value, knobs.align);                           \
     } while (0)
-#define LAUNCH_STEP(T, MODE, EMIT, VEC, NTL, NTS)                           \
+#define LAUNCH_STEP(T, MODE, EMIT, VEC, NTL, ST)                            \
     do {                                                                    \
-        if (epw == 2) LAUNCH_STEP_E(T, 2, MODE, EMIT, VEC, NTL, NTS);       \
-        else if (epw == 8) LAUNCH_STEP_E(T, 8, MODE, EMIT, VEC, NTL, NTS);  \
-        else if (epw == 1) LAUNCH_STEP_E(T, 1, MODE, EMIT, VEC, NTL, NTS);  \
-        else LAUNCH_STEP_E(T, 4, MODE, EMIT, VEC, NTL, NTS);                \
+        if (epw == 2) LAUNCH_STEP_E(T, 2, MODE, EMIT, VEC, NTL, ST);        \
+        else if (epw == 8) LAUNCH_STEP_E(T, 8, MODE, EMIT, VEC, NTL, ST);   \
+        else if (epw == 1) LAUNCH_STEP_E(T, 1, MODE, EMIT, VEC, NTL, ST);   \
+        else LAUNCH_STEP_E(T, 4, MODE, EMIT, VEC, NTL, ST);                 \
     } while (0)
 #define DISPATCH_T(T)                                                                       \
     do {                                                                                    \
-        if (!emit) LAUNCH_STEP_E(T, 4, 0, false, false, false, false);                      \
-        else if (!vec) LAUNCH_STEP(T, 0, true, false, false, false);                        \
-        else if (!staged) LAUNCH_STEP(T, 1, true, true, false, true);                       \
-        else if (chase && nts) LAUNCH_STEP(T, 3, true, true, true, true);                   \
-        else if (chase) LAUNCH_STEP(T, 3, true, true, true, false);                         \
-        else if (nts) LAUNCH_STEP(T, 2, true, true, true, true);                            \
-        else LAUNCH_STEP(T, 2, true, true, true, false);                                    \
+        if (!emit) LAUNCH_STEP_E(T, 4, 0, false, false, false, kStPlain);                   \
+        else if (!vec) LAUNCH_STEP(T, 0, true, false, false, kStPlain);                     \
+        else if (!staged) LAUNCH_STEP(T, 1, true, true, false, kStNt);                      \
+        else if (chase && nts) LAUNCH_STEP(T, 3, true, true, true, kStNt);                  \
+        else if (chase && wt) LAUNCH_STEP(T, 3, true, true, true, kStWt);                   \
+        else if (chase) LAUNCH_STEP(T, 3, true, true, true, kStPlain);                      \
+        else if (nts) LAUNCH_STEP(T, 2, true, true, true, kStNt);                           \
+        else if (wt) LAUNCH_STEP(T, 2, true, true, true, kStWt);                            \
+        else LAUNCH_STEP(T, 2, true, true, true, kStPlain);                                 \
     } while (0)
     RLS_REQUIRE(emit || epw == 4, RLS_EINVAL, "the in-place step runs 4 envs per wave");
     if (spin_bytes == 1) DISPATCH_T(uint8_t);

@@ -88,7 +88,12 @@ if pmc and a.bench_json and os.path.exists(a.bench_json):
                 # round 6: bench.py also runs the headline loop with nontemporal stores (roofline.hbm_only) -- the same workload on a
                 # second instantiation, far fewer launches.  The instantiation with the most launches is the headline's; the others
                 # are marked as variants of the same workload (bench.py matches `workload` only)
-                hits.sort(key=lambda k: -pmc[k].get("FETCH_SIZE_launches", 0))
+                # (round 7: the headline stores write-through below 256 MB, so the hbm_only loop -- nontemporal stores, last template
+                # argument `true` before round 7, `1` = kStNt since -- is no longer the same instantiation with fewer launches: it is
+                # ranked last by name when the line reports hbm_only)
+                hbm_only = "hbm_only" in line.get("roofline", {}) and envs == line["config"]["envs_per_gpu"]
+                nt_store = lambda k: k.replace(" ", "").endswith((",true>", ",1>"))
+                hits.sort(key=lambda k: (hbm_only and nt_store(k), -pmc[k].get("FETCH_SIZE_launches", 0)))
                 for k in hits[1:]:
                     pmc[k]["workload_variant"] = {"envs": envs, "nodes": nodes, "slots": slots, "of": hits[0]}
                     pmc[k]["algorithmic_bytes_per_launch"] = alg
