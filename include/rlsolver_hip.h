@@ -682,6 +682,13 @@ int rls_qubo_sparse_local_search_value(const int32_t* rowptr, const int32_t* col
                                        const float* xs_in, float* xs_out, int64_t C, int64_t num_ls, int binary,
                                        float* value, void* stream);
 
+/* [host] 1 when the K11 call of this form runs n variables x C chains within its LDS budget, else 0 (the call would return
+ * RLS_EUNSUPPORTED; an addition that changes no existing entry, so the ABI stays v12).  form 0: rls_qubo_local_search_value
+ * (dense); 1: rls_qubo_sparse_local_search_value without a level schedule; 2: with one (the level kernel, or the sequential
+ * kernel where the level kernel's LDS does not fit).  Both kernels accept any square Q -- symmetric or not, empty rows,
+ * nnz = 0 -- the sparse one with a level schedule built over the symmetrised pattern (Q_ij != 0 or Q_ji != 0). */
+int rls_qubo_local_search_supported(int64_t n, int64_t C, int32_t form);
+
 /* --------------------------------------------------------------------- TSP */
 
 /* K12 ISCO_TSP.calculate_distance(sample)  envs/env_ISCO.py:346-350.

@@ -669,6 +669,57 @@ def mcpg_sampling_maxcut(graph_w, num_nodes, sorted_degree_nodes, start_status, 
     return vs, x[:, index], start, expected - expected.mean(dtype=np.float32), expected
 
 
+# --------------------------------------------------------------------------- upstream MCPG QUBO sweep
+
+
+def qubo_csr(Q):
+    """Dense Q [n, n] -> (rowptr int64 [n+1], col int64 [nnz], val float64 [nnz]) of its nonzero entries, row by row."""
+    Q = np.asarray(Q, dtype=np.float64)
+    nz = Q != 0
+    rowptr = np.zeros(Q.shape[0] + 1, dtype=np.int64)
+    rowptr[1:] = np.cumsum(nz.sum(axis=1))
+    return rowptr, np.nonzero(nz)[1].astype(np.int64), Q[nz]
+
+
+def qubo_local_search_value(Q, xs, num_ls, binary, stats=None):
+    """The coordinate search and value of mcpg_sampling_qubo / mcpg_sampling_qubo_bin, rlsolver/methods/MCPG/sampling.py:
+    332-340 / :357-365, in float64, for ANY square Q (the reference neither symmetrises nor checks it):
+        for cnt < num_ls: for i < n:  s_i := 0;  res = Q[i, :] . s;  s_i := res > thr_i
+    with s in {-1, +1} and thr_i = 0 (binary = False: res == 0 gives -1) or s in {0, 1} and thr_i = -Q_ii / 2 (binary = True:
+    res == -Q_ii / 2 gives 0); then value = s^T Q s.
+    Q: a dense [n, n] array or a CSR triple (rowptr, col, val) -- the sweep walks the rows' nonzero entries either way, so
+    n = 20 000 at a few entries per row takes seconds.  xs 0/1 [n, C] (not modified).
+    -> (x float32 0/1 [n, C] (the reference's (s + 1) / 2 for +-1), value float64 [C]).  stats (a dict, optional) receives
+    "ties": the number of (row, chain) steps with res == thr exactly, where the strict '>' decided."""
+    rowptr, col, val = qubo_csr(Q) if not isinstance(Q, tuple) else (np.asarray(Q[0], np.int64), np.asarray(Q[1], np.int64),
+                                                                      np.asarray(Q[2], np.float64))
+    n = rowptr.size - 1
+    x0 = np.asarray(xs, dtype=np.float64)
+    assert x0.ndim == 2 and x0.shape[0] == n, "xs must be [n, C]"
+    s = x0.copy() if binary else 2.0 * x0 - 1.0
+    rows = [(col[rowptr[i]:rowptr[i + 1]], val[rowptr[i]:rowptr[i + 1]]) for i in range(n)]
+    diag = np.array([v[c == i].sum() for i, (c, v) in enumerate(rows)], dtype=np.float64)
+    ties = 0
+    for cnt in range(num_ls):
+        for i in range(n):
+            c, v = rows[i]
+            s[i] = 0.0
+            res = v @ s[c] if c.size else np.zeros(s.shape[1])
+            thr = -diag[i] / 2.0 if binary else 0.0
+            ties += int((res == thr).sum())
+            hit = res > thr
+            s[i] = hit if binary else 2.0 * hit - 1.0
+    value = np.zeros(s.shape[1])
+    for i in range(n):
+        c, v = rows[i]
+        if c.size:
+            value += s[i] * (v @ s[c])
+    if stats is not None:
+        stats["ties"] = ties
+    x = s if binary else (s + 1.0) / 2.0
+    return x.astype(np.float32), value
+
+
 # --------------------------------------------------------------------------- TSP true 2-opt local search
 
 

@@ -138,6 +138,7 @@ SIGNATURES = {
 PLAIN = {"rls_version": ([], _INT), "rls_device_count": ([], _INT), "rls_last_error_string": ([], C.c_char_p),
          "rls_maxcut_local_search_supported": ([_G, _I64, C.c_int32], _INT),
          "rls_mcpg_local_search_levels_supported": ([_G, _I64], _INT),
+         "rls_qubo_local_search_supported": ([_I64, _I64, C.c_int32], _INT),
          "rls_maxcut_ls_rounds_supported": ([_G, C.c_int32], _INT),
          "rls_maxcut_node_stats_form": ([_G, _I64, C.c_int32], _INT),
          "rls_mcpg_metro_max_rounds": ([_I64, C.c_int32], _I64),

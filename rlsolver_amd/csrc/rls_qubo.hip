@@ -366,8 +366,8 @@ __global__ __launch_bounds__(kWave) void k_qubo_sparse_ls_value(const int32_t* _
 // Sparse QUBO by LEVELS (round 6).  The kernel above is one wave per 64 chains walking the n rows in order: 2^13 chains are
 // 128 waves on a 1024-SIMD chip, 0.38 us per row -- 2.5 x slower than the dense MFMA kernel on a 2 %-filled 1000 x 1000 Q.  Row i
 // needs the NEW bits of its neighbours j < i and the OLD bits of its neighbours j > i, so with level(i) = 1 + max level of the
-// neighbours below i (host: MCPG_qubo.qubo_levels) the rows of one level have no entry between them and every neighbour above
-// a row sits in a later level: the W waves of a 64-chain workgroup take a level's rows side by side, one barrier per level, and
+// neighbours below i -- through Q_ij or Q_ji: Q need not be symmetric (host: MCPG_qubo.qubo_levels) -- the rows of one level
+// have no entry between them and every neighbour above a row sits in a later level: the W waves of a 64-chain workgroup take a level's rows side by side, one barrier per level, and
 // the result is the sequential sweep's bit for bit (the sums are order-independent for integer-valued Q, as everywhere in K11).
 // (Measured and not kept: the schedule and row bounds staged in LDS + the next level's first row requested before the barrier --
 // 487 -> 539 us at n = 1000, 2 % fill, 2^13 chains: the scalar cache already holds them, the time is the dependent VALU chain of a
@@ -496,22 +496,53 @@ __global__ __launch_bounds__(W * kWave) void k_qubo_sparse_levels(const int32_t*
         for (int64_t j = w; j < n; j += W) xs_out[j * C + c] = (float)((w32[(j << 1) + half] >> sh) & 1u);
 }
 
+// The launch plans, shared by the launchers and rls_qubo_local_search_supported (the one place that knows the LDS budgets).
+// Dense: 64-chain workgroups (half the L2 traffic and resolution work per chain) once they fill the chip; 8 waves (two per
+// SIMD, for the L2 latency) while a CU holds a single workgroup, 4 when several can share it.  LDS: the bit tile over n padded
+// to the waves' column split + the partial tiles -- n <= 30 720 (8 waves), 35 840 (4 waves), 15 872 (64-chain workgroups).
+struct QmPlan { bool nt2; int W; int64_t n_pad; size_t lds; };
+inline QmPlan qm_plan(int64_t n, int64_t C) {
+    QmPlan p;
+    p.nt2 = C >= (int64_t)2 * 64 * num_cus();
+    p.W = (!p.nt2 && ceil_div(C, 32) <= (int64_t)2 * num_cus()) ? 8 : 4;
+    p.n_pad = ceil_div(n, 32 * p.W) * 32 * p.W;
+    p.lds = (size_t)p.n_pad * (p.nt2 ? 8 : 4) + (size_t)p.W * 32 * (p.nt2 ? qm_part_stride<2>() : qm_part_stride<1>()) * 4;
+    return p;
+}
+// CSR by levels: W waves per 64-chain tile -- 16 while that leaves at most two waves per SIMD (a row's sums are a dependent
+// VALU chain: a second wave fills its issue gaps), 8 up to four, then 4 (RLS_QUBO_LEVELS = 4 / 8 / 16 forces one).  LDS: the
+// 64-chain words + the waves' partial values -- n <= 19 968 / 20 224 / 20 352 at W = 16 / 8 / 4.
+inline int ql_waves(int64_t C) {
+    const int64_t tiles = ceil_div(C, kWave);
+    const int kw = (int)knob(KN_QUBO_LEVELS, 1);
+    return kw == 4 || kw == 8 || kw == 16 ? kw : (tiles * 16 <= (int64_t)8 * num_cus() ? 16 : (tiles * 8 <= (int64_t)16 * num_cus() ? 8 : 4));
+}
+inline size_t ql_lds(int64_t n, int W) { return (size_t)n * 8 + (size_t)W * kWave * 4; }
+// CSR, one wave walking the rows in order: the words + rowptr -- n <= 13 653.
+inline size_t qs_lds(int64_t n) { return (size_t)n * 8 + (size_t)(n + 1) * 4; }
+
 }  // namespace rls
 
 using namespace rls;
+
+extern "C" int rls_qubo_local_search_supported(int64_t n, int64_t C, int32_t form) {
+    if (n <= 0 || C < 0 || form < 0 || form > 2) return 0;
+    if (C == 0) return 1;
+    if (form == 0) return qm_plan(n, C).lds <= (size_t)kLdsBytes;
+    if (form == 2 && knob(KN_QUBO_LEVELS, 1) != 0 && ql_lds(n, ql_waves(C)) <= (size_t)kLdsBytes) return 1;
+    return qs_lds(n) <= (size_t)kLdsBytes;
+}
 
 extern "C" int rls_qubo_local_search_value(const float* Q, int64_t n, const float* xs_in, float* xs_out, int64_t C,
                                            int64_t num_ls, int binary, float* value, void* stream) {
     RLS_REQUIRE(n > 0 && C >= 0 && num_ls >= 0, RLS_EINVAL, "bad sizes n=%lld C=%lld", (long long)n, (long long)C);
     if (C == 0) return RLS_OK;
     RLS_REQUIRE(Q && xs_in && xs_out && value, RLS_EINVAL, "NULL pointer");
-    // 64-chain workgroups (half the L2 traffic and resolution work per chain) once they fill the chip; 8 waves (two per
-    // SIMD, for the L2 latency) while a CU holds a single workgroup, 4 when several can share it
-    const bool nt2 = C >= (int64_t)2 * 64 * num_cus();
-    const bool w8 = !nt2 && ceil_div(C, 32) <= (int64_t)2 * num_cus();
-    const int W = w8 ? 8 : 4;
-    const int64_t n_pad = ceil_div(n, 32 * W) * 32 * W;
-    const size_t lds = (size_t)n_pad * (nt2 ? 8 : 4) + (size_t)W * 32 * (nt2 ? qm_part_stride<2>() : qm_part_stride<1>()) * 4;
+    const QmPlan pl = qm_plan(n, C);
+    const bool nt2 = pl.nt2, w8 = pl.W == 8;
+    const int W = pl.W;
+    const int64_t n_pad = pl.n_pad;
+    const size_t lds = pl.lds;
     RLS_REQUIRE(lds <= (size_t)kLdsBytes, RLS_EUNSUPPORTED, "n=%lld needs %zu B of LDS (max %d)", (long long)n, lds,
                 kLdsBytes);
     const dim3 grid((unsigned)ceil_div(C, nt2 ? 64 : 32)), block(W * kWave);
@@ -543,12 +574,10 @@ extern "C" int rls_qubo_sparse_local_search_value(const int32_t* rowptr, const i
     RLS_REQUIRE((lv_ptr != nullptr) == (lv_rows != nullptr) && (!lv_ptr || num_levels >= 1), RLS_EINVAL,
                 "lv_ptr / lv_rows / num_levels come together");
     if (lv_ptr && knob(KN_QUBO_LEVELS, 1) != 0) {
-        // the level schedule: W waves per 64-chain tile -- 16 while that leaves at most two waves per SIMD (a row's sums are a
-        // dependent VALU chain: a second wave fills its issue gaps), 8 up to four, then 4
+        // the level schedule (ql_waves: W waves per 64-chain tile); past its LDS budget, the sequential kernel below
         const int64_t tiles = ceil_div(C, kWave);
-        const int kw = (int)knob(KN_QUBO_LEVELS, 1);
-        const int Wv = kw == 4 || kw == 8 || kw == 16 ? kw : (tiles * 16 <= (int64_t)8 * num_cus() ? 16 : (tiles * 8 <= (int64_t)16 * num_cus() ? 8 : 4));
-        const size_t ldl = (size_t)n * 8 + (size_t)Wv * kWave * 4;
+        const int Wv = ql_waves(C);
+        const size_t ldl = ql_lds(n, Wv);
         if (ldl <= (size_t)kLdsBytes) {
             const dim3 gl((unsigned)tiles), bl(Wv * kWave);
 #define RLS_QL_LAUNCH(BIN_, W_)                                                                                                  \
@@ -565,7 +594,7 @@ extern "C" int rls_qubo_sparse_local_search_value(const int32_t* rowptr, const i
             return check_launch("k_qubo_sparse_levels");
         }
     }
-    const size_t lds = (size_t)n * 8 + (size_t)(n + 1) * 4;
+    const size_t lds = qs_lds(n);
     RLS_REQUIRE(lds <= (size_t)kLdsBytes, RLS_EUNSUPPORTED, "n=%lld needs %zu B of LDS (max %d)", (long long)n, lds, kLdsBytes);
     const dim3 grid((unsigned)ceil_div(C, kWave)), block(kWave);
     if (binary) {

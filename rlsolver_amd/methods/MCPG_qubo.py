@@ -8,6 +8,7 @@ from typing import Optional
 import numpy as np
 import torch
 
+from .. import _abi
 from ..ops import _check, _t
 from .MCPG import metro_sampling
 
@@ -59,19 +60,27 @@ def qubo_to_csr(Q: TEN, levels: bool = True):
 
 
 def qubo_levels(rowptr, col):
-    """Level schedule of the Gauss-Seidel sweep over a CSR pattern: level(i) = 1 + max(level(j): j < i, Q_ij != 0).  Rows of one
-    level share no entry and every neighbour above a row sits in a later level, so a level's rows can be updated side by side
-    with the sequential sweep's result.  -> (lv_ptr int32 [L + 1], lv_rows int32 [n]: rows by (level, index)), on rowptr's
-    device.  Host work, once per matrix."""
+    """Level schedule of the Gauss-Seidel sweep over a CSR pattern: level(i) = 1 + max(level(j): j < i, Q_ij != 0 or Q_ji != 0)
+    -- over the SYMMETRISED pattern, since Q need not be symmetric (the reference takes it as the file gives it): row i reads
+    word j when Q_ij != 0, and with Q_ji == 0 alone row j would not see row i as a neighbour and could land in i's level, its
+    wave rewriting word j while i's still reads it.  With the symmetrised pattern, rows of one level share no entry in either
+    direction and every neighbour above a row sits in a later level, so a level's rows can be updated side by side with the
+    sequential sweep's result.  For a symmetric Q this is the schedule over row i's own entries j < i.
+    -> (lv_ptr int32 [L + 1], lv_rows int32 [n]: rows by (level, index)), on rowptr's device.  Host work, once per matrix."""
     rp = rowptr.detach().cpu().numpy().astype(np.int64)
     cl = col.detach().cpu().numpy().astype(np.int64)
     n = rp.size - 1
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(rp))
+    hi, lo = np.maximum(rows, cl), np.minimum(rows, cl)
+    off = hi != lo
+    hi, lo = hi[off], lo[off]
+    order = np.argsort(hi, kind="stable")
+    hi, lo = hi[order], lo[order]
+    lptr = np.searchsorted(hi, np.arange(n + 1, dtype=np.int64))      # lo[lptr[i]:lptr[i + 1]]: the neighbours j < i of row i
     level = np.zeros(n, dtype=np.int64)
     for i in range(n):
-        nb = cl[rp[i]:rp[i + 1]]
-        nb = nb[nb < i]
-        if nb.size:
-            level[i] = level[nb].max() + 1
+        if lptr[i + 1] > lptr[i]:
+            level[i] = level[lo[lptr[i]:lptr[i + 1]]].max() + 1
     order = np.lexsort((np.arange(n), level))
     L = int(level.max()) + 1 if n else 1
     lv_ptr = np.zeros(L + 1, dtype=np.int32)
@@ -94,6 +103,8 @@ def qubo_sparse_local_search_value(csr, xs: TEN, num_ls: int, binary: bool):
     _check(xs, "xs", (torch.float32,), dev)
     if xs.dim() != 2 or xs.shape[0] != n:
         raise ValueError(f"xs must be [{n}, C]")
+    if col.numel() == 0:                 # Q = 0: no entry is ever read, but the library wants real pointers
+        col, val = torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.float32, device=dev)
     out = torch.empty_like(xs)
     value = torch.empty(xs.shape[1], dtype=torch.float32, device=dev)
     _t.qubo_sparse_local_search_value(rowptr, col, val, lv_ptr, lv_rows, xs, out, num_ls, bool(binary), value)
@@ -122,14 +133,29 @@ def qubo_prefers_sparse(n: int, nnz: int, num_chains: int) -> bool:
     return sparse_us < dense_us
 
 
+def qubo_supported(n: int, num_chains: int, form: str) -> bool:
+    """Whether the K11 kernel of this form runs n variables x num_chains chains within its LDS budget (the library's own
+    rule, rls_qubo_local_search_supported): "dense" (qubo_local_search_value), "csr" (qubo_sparse_local_search_value on a bare
+    CSR triple) or "levels" (with the level schedule)."""
+    return bool(_abi.lib().rls_qubo_local_search_supported(int(n), int(num_chains), {"dense": 0, "csr": 1, "levels": 2}[form]))
+
+
 def _sample(data, start_result, probs, num_ls, change_times, total_mcmc_num, device, binary, index, u):
     Q = data['Q'].to(device=device, dtype=torch.float32).contiguous()
     raw_samples = metro_sampling(probs, start_result, change_times, device, index=index, u=u)   # never modifies its input
+    n, C = Q.shape[0], raw_samples.shape[1]
     if 'csr' not in data:
         nnz = int((Q != 0).sum())
-        data['csr'] = qubo_to_csr(Q) if qubo_prefers_sparse(Q.shape[0], nnz, raw_samples.shape[1]) else None
-    if data.get('csr') is not None:
-        samples, res_sample = qubo_sparse_local_search_value(data['csr'], raw_samples.contiguous(), num_ls, binary)
+        sparse = qubo_supported(n, C, "levels") and (qubo_prefers_sparse(n, nnz, C) or not qubo_supported(n, C, "dense"))
+        data['csr'] = qubo_to_csr(Q) if sparse else None
+    csr = data['csr']
+    # never a kernel that refuses the shape while the other one runs it (the LDS budgets depend on the chain count too)
+    if csr is None and not qubo_supported(n, C, "dense") and qubo_supported(n, C, "levels"):
+        csr = qubo_to_csr(Q)
+    elif csr is not None and not qubo_supported(n, C, "levels" if len(csr) >= 5 else "csr") and qubo_supported(n, C, "dense"):
+        csr = None
+    if csr is not None:
+        samples, res_sample = qubo_sparse_local_search_value(csr, raw_samples.contiguous(), num_ls, binary)
     else:
         samples, res_sample = qubo_local_search_value(Q, raw_samples.contiguous(), num_ls, binary)
     res_reshape = res_sample.reshape(-1, total_mcmc_num)

@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 import torch
 
+from oracle import oracle_np as onp
 from rlsolver_amd.methods import MCPG_qubo as q
 from tests.gpu_util import DEV
 
@@ -17,7 +18,18 @@ def dev(a, dtype=None):
 @pytest.mark.parametrize("name", ["nbiq_5", "rand_24"])
 @pytest.mark.parametrize("mode", ["pm1", "bin"])
 def test_qubo_golden(golden, name, mode):
-    z = golden("qubo")
+    _check_golden(golden("qubo"), name, mode)
+
+
+@pytest.mark.parametrize("name", ["upper_30", "asym_32", "frac_20"])
+@pytest.mark.parametrize("mode", ["pm1", "bin"])
+def test_qubo_asym_golden(golden, name, mode):
+    """An upper-triangular Q, an asymmetric one and one in quarters with a fractional diagonal: the reference takes Q as given.
+    The sampler picks its kernel by itself; every kernel path on such matrices: test_gpu_qubo_general.py."""
+    _check_golden(golden("qubo_asym"), name, mode)
+
+
+def _check_golden(z, name, mode):
     data = {"Q": dev(z[f"{name}/Q"]), "nvar": z[f"{name}/Q"].shape[0]}
     fn = q.mcpg_sampling_qubo if mode == "pm1" else q.mcpg_sampling_qubo_bin
     max_res, best, raw, value = fn(data, dev(z[f"{name}/start"], torch.float32), dev(z[f"{name}/probs"]),
@@ -44,6 +56,8 @@ def test_qubo_value_is_quadratic_form_and_sweep_is_monotone():
         x2, v2 = q.qubo_local_search_value(Q, dev(x0), 3, binary)
         s2 = x2.cpu().numpy() if binary else 2 * x2.cpu().numpy() - 1
         assert np.array_equal(v2.cpu().numpy(), np.einsum("ic,ij,jc->c", s2, Qn, s2).astype(np.float32))
+        want_x, want_v = onp.qubo_local_search_value(Qn, x0, 3, binary)
+        assert np.array_equal(x2.cpu().numpy(), want_x) and np.array_equal(v2.cpu().numpy(), want_v.astype(np.float32))
         assert (v2 >= v1).all()                                          # symmetric Q: coordinate ascent never loses
 
 
@@ -60,14 +74,8 @@ def test_qubo_sparse_equals_dense_and_block_sweep_equals_sequential(n, C, densit
     csr = q.qubo_to_csr(Q)
     assert int(csr[0][-1]) == int((Qn != 0).sum())
     for binary in (False, True):
-        s = x0.copy() if binary else 2 * x0 - 1
-        for cnt in range(2):                                                   # the reference's loop, sampling.py:332-337
-            for i in range(n):
-                s[i] = 0
-                res = Qn[i] @ s
-                s[i] = ((res > -Qn[i, i] / 2).astype(np.float32)) if binary else (2 * (res > 0) - 1).astype(np.float32)
-        want_x = s if binary else (s + 1) / 2
-        want_v = np.einsum("ic,ij,jc->c", s, Qn, s).astype(np.float32)
+        want_x, want_v = onp.qubo_local_search_value(Qn, x0, 2, binary)       # the reference's loop, sampling.py:332-337
+        want_v = want_v.astype(np.float32)
         xd, vd = q.qubo_local_search_value(Q, dev(x0), 2, binary)
         xs_, vs_ = q.qubo_sparse_local_search_value(csr, dev(x0), 2, binary)            # by levels: the waves of a workgroup side by side
         xq_, vq_ = q.qubo_sparse_local_search_value(csr[:3], dev(x0), 2, binary)        # one wave walking the rows in order
@@ -125,14 +133,8 @@ def test_qubo_dense_kernel_variants_equal_the_sequential_sweep(n, C):
     x0 = rng.randint(0, 2, size=(n, C)).astype(np.float32)
     Q = dev(Qn)
     for binary in (False, True):
-        s = x0.copy() if binary else 2 * x0 - 1
-        for cnt in range(2):
-            for i in range(n):
-                s[i] = 0
-                res = Qn[i] @ s
-                s[i] = ((res > -Qn[i, i] / 2).astype(np.float32)) if binary else (2 * (res > 0) - 1).astype(np.float32)
-        want_x = s if binary else (s + 1) / 2
-        want_v = np.einsum("ic,ij,jc->c", s, Qn, s).astype(np.float32)
+        want_x, want_v = onp.qubo_local_search_value(Qn, x0, 2, binary)
+        want_v = want_v.astype(np.float32)
         xd, vd = q.qubo_local_search_value(Q, dev(x0), 2, binary)
         assert np.array_equal(xd.cpu().numpy(), want_x)
         assert np.array_equal(vd.cpu().numpy(), want_v)

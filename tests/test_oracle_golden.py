@@ -406,3 +406,33 @@ def test_oracle_on_toroidal_gset_known_answer(golden, k, rows, cols):
     for bidir in (False, True):
         got = onp.maxcut_obj(np.stack([x, 1 - x]), graph, bidir)
         assert got.tolist() == [int(z[f"kat/G{k}/claimed_cut"])] * 2
+
+
+def _qubo_against_oracle(z, name, mode):
+    """The oracle's sweep + value on the recorded metro output (raw) gives what the reference's sampler returned."""
+    Q = z[f"{name}/Q"]
+    M, num_ls = int(z[f"{name}/M"]), int(z[f"{name}/num_ls"])
+    x, v = onp.qubo_local_search_value(Q, z[f"{name}/{mode}/raw"], num_ls, mode == "bin")
+    idx = np.arange(M) + v.reshape(-1, M).argmax(axis=0) * M
+    assert np.array_equal(v[idx].astype(np.float32), z[f"{name}/{mode}/max_res"]), (name, mode)
+    assert np.array_equal(x[:, idx], z[f"{name}/{mode}/best"]), (name, mode)
+    np.testing.assert_allclose(-(v - v.mean()), z[f"{name}/{mode}/value"], rtol=1e-6, atol=1e-3)
+    # the CSR form of the same matrix walks the same entries
+    x2, v2 = onp.qubo_local_search_value(onp.qubo_csr(Q), z[f"{name}/{mode}/raw"], num_ls, mode == "bin")
+    assert np.array_equal(x2, x) and np.array_equal(v2, v)
+
+
+@pytest.mark.parametrize("name", ["nbiq_5", "rand_24"])
+@pytest.mark.parametrize("mode", ["pm1", "bin"])
+def test_qubo_sweep_oracle(golden, name, mode):
+    _qubo_against_oracle(golden("qubo"), name, mode)
+
+
+@pytest.mark.parametrize("name", ["upper_30", "asym_32", "frac_20"])
+@pytest.mark.parametrize("mode", ["pm1", "bin"])
+def test_qubo_sweep_oracle_on_asymmetric_matrices(golden, name, mode):
+    """The reference takes Q as given: triangular, asymmetric, quarters with a fractional diagonal."""
+    z = golden("qubo_asym")
+    Q = z[f"{name}/Q"]
+    assert not np.array_equal(Q, Q.T) or np.any(Q != np.round(Q))
+    _qubo_against_oracle(z, name, mode)

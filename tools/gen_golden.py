@@ -681,6 +681,25 @@ def gen_qubo():
     """mcpg_sampling_qubo / _qubo_bin of rlsolver/methods/MCPG/sampling.py:323-370 on nbiq_5 and on a
     seeded integer Q (n = 24, nbiq-style: symmetric, 80 % dense, entries +-[10, 100]); rand/randint
     draws of the embedded metro_sampling recorded."""
+    smp = _load_mcpg_sampling()
+    out = {}
+    rows = [[float(v) for v in line.replace(" ", "").strip().strip(",").split(",")]
+            for line in open(os.path.join(DATA, "qubo", "nbiq_5.txt")) if line.strip()]
+    rng = np.random.RandomState(24)
+    n = 24
+    Q = np.zeros((n, n))
+    for i in range(n):
+        for j in range(i, n):
+            if rng.rand() < 0.8:
+                v = rng.randint(10, 101) * (1 if rng.rand() < 0.5 else -1)
+                Q[i, j] = Q[j, i] = v
+    cases = {"nbiq_5": np.asarray(rows, dtype=np.float64), "rand_24": Q}
+    _run_qubo_samplers(smp, cases, out)
+    save("qubo", **out)
+
+
+def _load_mcpg_sampling():
+    """rlsolver/methods/MCPG/sampling.py, with a stand-in for torch_scatter (MaxSAT only) and its package's config.py."""
     ts = types.ModuleType("torch_scatter")
     ts.scatter = lambda *a, **k: (_ for _ in ()).throw(NotImplementedError("MaxSAT only"))
     sys.modules.setdefault("torch_scatter", ts)
@@ -696,18 +715,11 @@ def gen_qubo():
         sys.modules.pop("config", None)
         if saved_cfg is not None:
             sys.modules["config"] = saved_cfg
-    out = {}
-    rows = [[float(v) for v in line.replace(" ", "").strip().strip(",").split(",")]
-            for line in open(os.path.join(DATA, "qubo", "nbiq_5.txt")) if line.strip()]
-    rng = np.random.RandomState(24)
-    n = 24
-    Q = np.zeros((n, n))
-    for i in range(n):
-        for j in range(i, n):
-            if rng.rand() < 0.8:
-                v = rng.randint(10, 101) * (1 if rng.rand() < 0.5 else -1)
-                Q[i, j] = Q[j, i] = v
-    cases = {"nbiq_5": np.asarray(rows, dtype=np.float64), "rand_24": Q}
+    return smp
+
+
+def _run_qubo_samplers(smp, cases, out):
+    """Both samplers on every Q of `cases`, the start state / probs seeded per case and the draws recorded."""
     for name, Qn in cases.items():
         nvar = Qn.shape[0]
         data = {"Q": th.tensor(Qn).float(), "nvar": nvar}
@@ -732,7 +744,30 @@ def gen_qubo():
             out[f"{name}/{mode}/best"] = best.numpy().copy()
             out[f"{name}/{mode}/raw"] = u8(raw)
             out[f"{name}/{mode}/value"] = value.numpy().copy()
-    save("qubo", **out)
+
+
+def gen_qubo_asym():
+    """The same samplers on matrices the reference takes as given and the symmetric fixtures never reach (its loader,
+    MCPG/dataloader.py:278-294, neither symmetrises nor checks Q; sampling.py:332-337 / :357-362 read row i only): an
+    upper-triangular Q (the triangular storage nbiq_gen.py builds before symmetrising), an asymmetric Q with a random
+    pattern (Q_ij != 0 with Q_ji == 0 in both triangles) and a Q in multiples of 1/4 with a fractional diagonal (every
+    float32 sum exact)."""
+    smp = _load_mcpg_sampling()
+    rng = np.random.RandomState(2606)
+    n = 30
+    A = rng.randint(1, 21, size=(n, n)) * np.where(rng.rand(n, n) < 0.5, 1, -1) * (rng.rand(n, n) < 0.5)
+    upper = np.triu(A).astype(np.float64)
+    n = 32
+    A = rng.randint(1, 31, size=(n, n)) * np.where(rng.rand(n, n) < 0.5, 1, -1) * (rng.rand(n, n) < 0.4)
+    drop = rng.rand(n, n) < 0.5
+    asym = np.where(drop & ~drop.T & ~np.eye(n, dtype=bool), 0, A).astype(np.float64)
+    n = 20
+    A = rng.randint(-40, 41, size=(n, n)) * (rng.rand(n, n) < 0.6) / 4.0
+    frac = np.triu(A, 1) + np.triu(A, 1).T
+    np.fill_diagonal(frac, (2 * rng.randint(-20, 21, size=n) + 1) / 4.0)           # odd quarters: never an integer
+    out = {}
+    _run_qubo_samplers(smp, {"upper_30": upper, "asym_32": asym, "frac_20": frac}, out)
+    save("qubo_asym", **out)
 
 
 def _load_upstream_mcpg(modname):
@@ -1477,7 +1512,7 @@ def gen_api_surface():
     save("api_surface", surface=np.array(json.dumps(surface, sort_keys=True, indent=0)))
 
 
-ALL = {"mcpg_weighted": gen_mcpg_weighted, "isco_steps": gen_isco_steps, "spinsystem_cpu": gen_spinsystem_cpu, "spinsystem": gen_spinsystem, "spinsystem_perenv": gen_spinsystem_perenv, "qubo": gen_qubo, "isco_maxcut": gen_isco_maxcut, "maxcut": gen_maxcut, "sweep": gen_sweep, "lsclass": gen_local_search_class, "ppo": gen_ppo,
+ALL = {"mcpg_weighted": gen_mcpg_weighted, "isco_steps": gen_isco_steps, "spinsystem_cpu": gen_spinsystem_cpu, "spinsystem": gen_spinsystem, "spinsystem_perenv": gen_spinsystem_perenv, "qubo": gen_qubo, "qubo_asym": gen_qubo_asym, "isco_maxcut": gen_isco_maxcut, "maxcut": gen_maxcut, "sweep": gen_sweep, "lsclass": gen_local_search_class, "ppo": gen_ppo,
        "select": gen_select, "mcpg": gen_mcpg, "tsp": gen_tsp, "tsp_2opt": gen_tsp_2opt, "encoder": gen_encoder,
        "wgain": gen_weighted_gain, "mcpg_glue": gen_mcpg_glue, "evaluator": gen_evaluator, "spinsystem_options": gen_spinsystem_options,
        "api_surface": gen_api_surface, "mcpg_data": gen_mcpg_data,
