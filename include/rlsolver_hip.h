@@ -53,9 +53,11 @@ enum {
 typedef struct rls_graph {
     int64_t num_nodes;        /* N */
     int64_t num_stored_edges; /* E' */
-    int64_t nnz;              /* 2E (symmetric CSR, self loops dropped) */
+    int64_t nnz;              /* entries of the symmetric CSR: 2E less the self loops, which the env graphs drop; the
+                               * MCPG / ISCO graphs list a loop twice in its row instead (build_csr keep_loops), so 2E */
     int32_t if_bidirectional; /* result of objective kernels is count / 2 when set */
-    int32_t max_degree;
+    int32_t max_degree;       /* an UPPER BOUND on every row length: the largest row of either adjacency (the stored
+                               * out-degree counts loops, the symmetric CSR may not); readers use it only as a bound */
     const int32_t* eu;        /* [E'] edge endpoints as stored, sorted by (eu, ev) */
     const int32_t* ev;        /* [E'] */
     const int32_t* erowptr;   /* [N+1] offsets of each node's run in eu/ev (the env's adjacency_indies) */

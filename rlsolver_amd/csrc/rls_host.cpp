@@ -379,7 +379,7 @@ int rls_mcpg_visit_levels(const int32_t* rowptr, const int32_t* col, int64_t N, 
         for (int32_t j = rowptr[i]; j < rowptr[i + 1]; ++j) {
             const int32_t q = pos_of[(size_t)col[j]];
             if (q < p) { if (level[(size_t)q] + 1 > l) l = level[(size_t)q] + 1; }
-            else if (q > p) ++nf;
+            else ++nf;      // (q == p: a self loop -- no dependency, and the node's own value is still undecided in pass 0)
         }
         level[(size_t)p] = l;
         nfresh[(size_t)p] = nf;
@@ -403,7 +403,7 @@ int rls_mcpg_visit_levels(const int32_t* rowptr, const int32_t* col, int64_t N, 
     };
     auto entry = [&](int32_t p, int32_t r) {   // r-th neighbour word of position p
         const int32_t i = order[p], nb = col[rowptr[i] + r];
-        return (int32_t)(((uint32_t)nb * 8u) | (pos_of[(size_t)nb] > p ? 0x80000000u : 0u));   // LDS byte offset of the word
+        return (int32_t)(((uint32_t)nb * 8u) | (pos_of[(size_t)nb] >= p ? 0x80000000u : 0u));  // LDS byte offset of the word
     };
     // Record layout (round 5): LANE-major, so that a lane fetches its data in a few wide loads instead of one dword per row --
     // dwords [2 l, 2 l + 1] = lane l's two header words (one 8-byte load), then per block of 8 rounds two slabs of [64 lanes][4

@@ -38,7 +38,9 @@ class ISCO_maxcut(Sharded):
         self.num_edges = params_dict['num_edges']
         eu = self.edge_from.detach().cpu().numpy().astype(np.int64)
         ev = self.edge_to.detach().cpu().numpy().astype(np.int64)
-        csr = build_csr((eu, ev, np.ones_like(eu)), num_nodes=self.max_num_nodes, if_bidirectional=False)
+        # a loop listed twice in its row: each adds +1/T to its node's score, as the reference's autograd energy does
+        # (its gain entries never differ, its two degree entries count)
+        csr = build_csr((eu, ev, np.ones_like(eu)), num_nodes=self.max_num_nodes, if_bidirectional=False, keep_loops=True)
         self.graph = ops.DeviceGraph(csr, self.device)
 
     def random_gen_init_sample(self, params_dict=None):

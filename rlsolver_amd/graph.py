@@ -255,7 +255,16 @@ class GraphCSR:
                ``if_bidirectional``; ordering = the reference's n0-major,
                n1-sorted order, env_L2A.py:46-48) -- objective kernels.
     rowptr/col/wgt : symmetric CSR over all N nodes, neighbours sorted,
-               multi-edges kept, self loops dropped -- delta kernels.
+               multi-edges kept, self loops dropped -- delta kernels.  With
+               ``build_csr(.., keep_loops=True)`` a loop (i, i) is listed twice in
+               row i instead, as the MCPG / ISCO neighbour lists of the reference
+               hold it (MCPG.py:235-252; the autograd energy of env_ISCO.py).
+    max_degree : the largest row of EITHER adjacency.  A self loop is dropped from
+               the symmetric CSR but counts in the stored out-degree (n0_num_n1,
+               the local-search weights), once per stored copy; on a loop-free
+               graph the stored out-degree never exceeds the symmetric degree,
+               so there this is the symmetric CSR's largest row.  Kernels read it
+               as an upper bound (entry widths, LDS budgets) only.
     """
     num_nodes: int
     num_edges: int            # len(mygraph)
@@ -281,8 +290,9 @@ class GraphCSR:
         return np.diff(self.rowptr)
 
 
-def build_csr(mygraph_or_arrays, num_nodes: int = 0, if_bidirectional: bool = False) -> GraphCSR:
-    """MyGraph (or (eu, ev, w) arrays) -> GraphCSR."""
+def build_csr(mygraph_or_arrays, num_nodes: int = 0, if_bidirectional: bool = False, keep_loops: bool = False) -> GraphCSR:
+    """MyGraph (or (eu, ev, w) arrays) -> GraphCSR.  ``keep_loops``: a self loop stays in the symmetric CSR, listed twice
+    (the neighbour rows of the MCPG samplers and of ISCO's MaxCut scores); by default it is dropped there (the flip gain of K3)."""
     if isinstance(mygraph_or_arrays, tuple) and len(mygraph_or_arrays) == 3 and isinstance(
             mygraph_or_arrays[0], np.ndarray):
         u, v, w = (np.asarray(a, dtype=np.int64) for a in mygraph_or_arrays)
@@ -311,21 +321,22 @@ def build_csr(mygraph_or_arrays, num_nodes: int = 0, if_bidirectional: bool = Fa
     order = np.lexsort((sv, su)) if su.size else np.zeros(0, np.int64)
     eu, ev, ew = su[order], sv[order], sw[order]
 
-    # symmetric CSR (self loops dropped)
-    keep = u != v
+    # symmetric CSR (self loops dropped, or listed twice)
+    keep = np.ones(E, dtype=bool) if keep_loops else u != v
     cu = np.concatenate([u[keep], v[keep]])
     cv = np.concatenate([v[keep], u[keep]])
     cw = np.concatenate([w[keep], w[keep]])
     o2 = np.lexsort((cv, cu)) if cu.size else np.zeros(0, np.int64)
     cu, cv, cw = cu[o2], cv[o2], cw[o2]
     counts = np.bincount(cu, minlength=num_nodes) if cu.size else np.zeros(num_nodes, np.int64)
+    st_counts = np.bincount(eu, minlength=num_nodes) if eu.size else np.zeros(num_nodes, np.int64)
     rowptr = np.zeros(num_nodes + 1, dtype=np.int64)
     np.cumsum(counts, out=rowptr[1:])
     return GraphCSR(
         num_nodes=int(num_nodes), num_edges=E, if_bidirectional=bool(if_bidirectional),
         eu=eu.astype(np.int32), ev=ev.astype(np.int32), ew=ew.astype(np.int32),
         rowptr=rowptr.astype(np.int32), col=cv.astype(np.int32), wgt=cw.astype(np.int32),
-        max_degree=int(counts.max()) if num_nodes else 0,
+        max_degree=max(int(counts.max()), int(st_counts.max())) if num_nodes else 0,
     )
 
 

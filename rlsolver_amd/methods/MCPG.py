@@ -74,7 +74,8 @@ def make_data(num_nodes: int, eu, ev, device, sorted_degree_nodes=None):
     device = torch.device(device)
     eu = np.asarray(eu, dtype=np.int64)
     ev = np.asarray(ev, dtype=np.int64)
-    csr = build_csr((eu, ev, np.ones_like(eu)), num_nodes=num_nodes, if_bidirectional=False)
+    # neighbour rows as append_neighbors lists them (MCPG.py:235-252): a loop twice, so the node's own value enters its sum twice
+    csr = build_csr((eu, ev, np.ones_like(eu)), num_nodes=num_nodes, if_bidirectional=False, keep_loops=True)
     # the objective kernel walks the edge list in file order semantics (order is irrelevant to a sum)
     data = MCPGData()
     data.num_nodes = num_nodes
@@ -145,7 +146,7 @@ def build_visit_stream(csr, order: np.ndarray, max_nodes: int = 32, max_entries:
     nbr = csr.col[idx].astype(np.int64)
     wgt = csr.wgt[idx].astype(np.int64)
     row_pos = np.repeat(np.arange(n), deg_o)
-    fresh = pos_of[nbr] > row_pos
+    fresh = pos_of[nbr] >= row_pos                                   # (a loop: the node itself, not yet decided in pass 0)
     nfresh = np.bincount(row_pos, weights=fresh * (wgt if weighted else 1), minlength=n).astype(np.int64)
     wdeg = np.bincount(row_pos, weights=wgt, minlength=n).astype(np.int64)
     # level schedule over visiting positions (graph relabelled by position); a record is hdr - 1 entries longer than

@@ -38,7 +38,7 @@ def make_data(num_nodes: int, eu, ev, w, device, sorted_degree_nodes=None):
     if np.any(w != np.round(w)):
         raise ValueError("the weighted MCPG sampler takes integer edge weights")
     wi = w.astype(np.int64)
-    csr = build_csr((eu, ev, wi), num_nodes=num_nodes, if_bidirectional=False)
+    csr = build_csr((eu, ev, wi), num_nodes=num_nodes, if_bidirectional=False, keep_loops=True)   # (a loop twice in its row)
     data = types.SimpleNamespace()
     data.num_nodes = num_nodes
     data.edge_index = torch.from_numpy(np.stack([eu, ev])).to(device)

@@ -57,6 +57,20 @@ def test_csr_edge_cases():
     assert csr.degree.tolist() == [2, 2, 0, 0] and csr.max_degree == 2
     with pytest.raises(ValueError):
         G.build_csr([(0, 5, 1)], num_nodes=3)
+    # a loop counts in the stored out-degree (once, twice when bidirectional): max_degree bounds both adjacencies
+    hub = [(0, j, 1) for j in range(1, 128)] + [(0, 0, 1)]
+    for bidir, st in ((False, 128), (True, 129)):
+        c = G.build_csr(hub, num_nodes=128, if_bidirectional=bidir)
+        assert c.degree.max() == 127 and np.bincount(c.eu)[0] == st and c.max_degree == st
+    # keep_loops (the MCPG / ISCO neighbour rows): the loop listed twice in its row, stored edges unchanged
+    k = G.build_csr([(1, 0, 1), (2, 2, 1), (0, 1, 1)], num_nodes=3, keep_loops=True)
+    assert k.degree.tolist() == [2, 2, 2] and k.col[k.rowptr[2]:k.rowptr[3]].tolist() == [2, 2]
+    assert k.eu.tolist() == [0, 1, 2] and k.ev.tolist() == [1, 0, 2]
+    # a loop-free graph keeps its max_degree (the symmetric one)
+    g = G.generate_gnm(300, 2000, 5)
+    for bidir in (False, True):
+        c = G.build_csr(g, num_nodes=300, if_bidirectional=bidir)
+        assert c.max_degree == c.degree.max() and c.max_degree == G.build_csr(g, num_nodes=300, keep_loops=True).degree.max()
     e = G.build_csr([], num_nodes=3)
     assert e.nnz == 0 and e.rowptr.tolist() == [0, 0, 0, 0]
 

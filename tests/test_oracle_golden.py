@@ -436,3 +436,59 @@ def test_qubo_sweep_oracle_on_asymmetric_matrices(golden, name, mode):
     Q = z[f"{name}/Q"]
     assert not np.array_equal(Q, Q.T) or np.any(Q != np.round(Q))
     _qubo_against_oracle(z, name, mode)
+
+
+# ------------------------------------------------------------------ graph forms: loops, repeated edges, n0 > n1 lines
+@pytest.mark.parametrize("name", ["small", "mid", "hub"])
+@pytest.mark.parametrize("bidir", [0, 1])
+def test_graph_forms_maxcut_and_local_search_pinned(golden, name, bidir):
+    """stored_edges / adjacency_lists, the objective, cut degree, local_search_inplace (num_iters 0 and 8) and
+    LocalSearch.random_search reproduce the reference on edge lists with loops, repeats and n0 > n1 lines."""
+    z = golden("maxcut_graph_forms")
+    graph = z[f"{name}/graph"]
+    tag = f"{name}/bidir{bidir}"
+    n = int(z[f"{tag}/num_nodes"])
+    assert n == onp.num_nodes_distinct(graph)
+    u, _ = onp.stored_edges(graph, bool(bidir))
+    assert np.array_equal(np.bincount(u, minlength=n)[None, :], z[f"{tag}/n0_num_n1"])
+    xs = z[f"{tag}/xs"].astype(bool)
+    assert np.array_equal(onp.maxcut_obj(xs, graph, bool(bidir)), z[f"{tag}/obj"])
+    assert np.array_equal(onp.maxcut_obj_for_loop(xs, graph, n, bool(bidir)), z[f"{tag}/obj_loop"])
+    assert np.array_equal(onp.maxcut_node_cutdeg(xs, graph, n, bool(bidir)).astype(z[f"{tag}/cutdeg"].dtype) /
+                          (2 if bidir else 1), z[f"{tag}/cutdeg"])
+    for iters in (0, 8):
+        wx, wv = onp.local_search_inplace(xs.copy(), graph, n, bool(bidir), z[f"{tag}/ls{iters}/noise"], num_iters=iters,
+                                          num_spin=4, noise_std=0.3)
+        assert np.array_equal(wx.astype(np.uint8), z[f"{tag}/ls{iters}/xs_out"]) and np.array_equal(wv, z[f"{tag}/ls{iters}/vs_out"])
+    if not bidir:
+        gx, gv, _ = onp.local_search_class_random_search(xs.copy(), onp.maxcut_obj(xs, graph, False), graph, n,
+                                                         z[f"{tag}/rs/noise"], 4, 4, noise_std=0.3)
+        assert np.array_equal(gx.astype(np.uint8), z[f"{tag}/rs/xs"]) and np.array_equal(gv, z[f"{tag}/rs/vs"])
+
+
+@pytest.mark.parametrize("name", ["small", "mid", "hub"])
+def test_graph_forms_mcpg_sampler_pinned(golden, name):
+    """sampler_func with the reference's loader: a loop is listed twice among its node's neighbours."""
+    z = golden("maxcut_graph_forms")
+    t = f"{name}/mcpg"
+    ei = z[f"{t}/edge_index"]
+    n = int(z[f"{name}/bidir0/num_nodes"])
+    assert np.array_equal(ei.T, z[f"{name}/graph"][:, :2])
+    uni = z[f"{t}/uniforms"]
+    vs, xg, val, _, _ = onp.sampler_func(ei, n, z[f"{t}/sorted_degree_nodes"], z[f"{t}/xs_in"].astype(np.float32), uni.shape[0],
+                                         4, 2, uni)
+    assert np.array_equal(vs, z[f"{t}/vs_good"]) and np.array_equal(xg, z[f"{t}/xs_good"])
+    np.testing.assert_allclose(val, z[f"{t}/value"], rtol=0, atol=1e-5)
+
+
+def test_graph_forms_isco_local_dist_pinned(golden):
+    """ISCO get_local_dist on what the reference's loader makes of a file with repeated lines ((0, 0) padding rows)."""
+    from oracle import oracle_isco as oi
+    z = golden("maxcut_graph_forms")
+    ef, et = z["isco/edge_from"], z["isco/edge_to"]
+    assert ((ef == 0) & (et == 0)).sum() >= 2
+    x = z["isco/x"].astype(np.float32)
+    for T in (1.0, 0.37):
+        e, lp = oi.maxcut_local_dist(x, ef, et, T)
+        np.testing.assert_allclose(e, z[f"isco/T{T}/energy"], rtol=1e-6)
+        np.testing.assert_allclose(lp, z[f"isco/T{T}/log_prob"], rtol=1e-5, atol=1e-5)

@@ -1512,7 +1512,103 @@ def gen_api_surface():
     save("api_surface", surface=np.array(json.dumps(surface, sort_keys=True, indent=0)))
 
 
-ALL = {"mcpg_weighted": gen_mcpg_weighted, "isco_steps": gen_isco_steps, "spinsystem_cpu": gen_spinsystem_cpu, "spinsystem": gen_spinsystem, "spinsystem_perenv": gen_spinsystem_perenv, "qubo": gen_qubo, "qubo_asym": gen_qubo_asym, "isco_maxcut": gen_isco_maxcut, "maxcut": gen_maxcut, "sweep": gen_sweep, "lsclass": gen_local_search_class, "ppo": gen_ppo,
+# ----------------------------------------------------------------------------- graph forms (loops, repeats, n0 > n1)
+def _forms_lists():
+    """Edge lists (0-based, in file order) with self loops (one on a node with no other edge, one repeated), an edge repeated
+    in the same and in the opposite orientation, lines with n0 > n1, shuffled order, every id 0..N-1 appearing; and a hub of
+    127 neighbours stored as (hub, j) plus a loop: stored degree 128 (129 bidirectional) over a symmetric degree of 127."""
+    rng = np.random.RandomState(4242)
+    small = [(3, 1), (0, 0), (1, 3), (2, 5), (5, 2), (2, 5), (7, 7), (4, 6), (6, 4), (9, 8), (8, 0), (11, 11), (10, 3),
+             (2, 10), (1, 9), (4, 4), (4, 4), (7, 6), (0, 5)]
+    a, b = rng.randint(0, 39, 90), rng.randint(0, 39, 90)
+    mid = [(int(x), int(y)) for x, y in zip(a, b)] + [(39, 39), (12, 12), (5, 30), (30, 5), (5, 30)]
+    mid += [(i, i + 1) for i in range(39)]
+    mid = [mid[i] for i in rng.permutation(len(mid))]
+    hub = [(0, j) for j in range(1, 128)] + [(0, 0)] + [(j, j + 1) for j in range(1, 127, 3)]
+    hub = [hub[i] for i in rng.permutation(len(hub))]
+    return {"small": small, "mid": mid, "hub": hub}
+
+
+def gen_graph_forms():
+    """EnvMaxcut (both flavours), local_search_inplace, LocalSearch.random_search, sampler_func and ISCO get_local_dist on
+    edge lists with loops, repeats and n0 > n1 lines, read from files by the reference's own loaders."""
+    import tempfile
+    from rlsolver.envs.env_L2A import EnvMaxcut
+    from rlsolver.methods.LocalSearch import LocalSearch
+    from rlsolver.methods.util_read_data import read_mygraph
+    m = load_mcpg_module()
+    out = {}
+    tmp = tempfile.mkdtemp()
+    for name, edges in _forms_lists().items():
+        n = 1 + max(max(e) for e in edges)
+        path = os.path.join(tmp, name + ".txt")
+        with open(path, "w") as f:
+            f.write(f"{n} {len(edges)}\n" + "".join(f"{u + 1} {v + 1} 1\n" for u, v in edges))
+        mygraph = read_mygraph(path)
+        out[f"{name}/graph"] = graph_arrays(mygraph)
+        for bidir in (False, True):
+            env = EnvMaxcut(mygraph=mygraph, device=th.device("cpu"), if_bidirectional=bidir)
+            tag = f"{name}/bidir{int(bidir)}"
+            out[f"{tag}/num_nodes"] = np.int64(env.num_nodes)
+            out[f"{tag}/n0_num_n1"] = env.n0_num_n1.numpy().copy()
+            th.manual_seed(3)
+            xs0 = env.generate_xs_randomly(num_sims=16)
+            xs0[0] = 0                                       # nothing cut: every weight at its largest
+            out[f"{tag}/xs"] = u8(xs0)
+            out[f"{tag}/obj"] = env.calculate_obj_values(xs0).numpy().copy()
+            out[f"{tag}/obj_loop"] = env.calculate_obj_values_for_loop(xs0, if_sum=True).numpy().copy()
+            out[f"{tag}/cutdeg"] = env.calculate_obj_values_for_loop(xs0, if_sum=False).numpy().copy()
+            for iters in (0, 8):
+                with Recorder("randn_like") as rec:
+                    gx, gv = env.local_search_inplace(xs0.clone(), th.empty(()), num_iters=iters, num_spin=4, noise_std=0.3)
+                out[f"{tag}/ls{iters}/noise"] = th.stack(rec.log["randn_like"]).numpy().copy()
+                out[f"{tag}/ls{iters}/xs_out"] = u8(gx)
+                out[f"{tag}/ls{iters}/vs_out"] = gv.numpy().copy()
+            if not bidir:                                    # (the reference raises on a bidirectional env here)
+                ls = LocalSearch(simulator=env, num_nodes=env.num_nodes)
+                ls.reset(xs0.clone())
+                with Recorder("randn_like") as rec:
+                    gx, gv, _ = ls.random_search(num_iters=4, num_spin=4, noise_std=0.3)
+                out[f"{tag}/rs/noise"] = th.stack(rec.log["randn_like"]).numpy().copy()
+                out[f"{tag}/rs/xs"] = u8(gx)
+                out[f"{tag}/rs/vs"] = gv.numpy().copy()
+        # MCPG: the reference's loader (loops listed twice by append_neighbors) and sampler_func
+        data, num_nodes = m.maxcut_dataloader(path, device=th.device("cpu"))
+        out[f"{name}/mcpg/sorted_degree_nodes"] = data.sorted_degree_nodes.numpy().copy()
+        out[f"{name}/mcpg/edge_index"] = data.edge_index.numpy().copy()
+        M, R, num_ls = 4, 2, 2
+        g = th.Generator().manual_seed(9)
+        xs = th.randint(0, 2, (num_nodes, M * R), generator=g).float()
+        with Recorder("rand") as rec:
+            vs_good, xs_good, value = m.sampler_func(data, xs.clone(), num_ls, M, R, device=th.device("cpu"))
+        out[f"{name}/mcpg/xs_in"] = u8(xs)
+        out[f"{name}/mcpg/uniforms"] = th.stack(rec.log["rand"]).numpy().copy().reshape(num_ls, num_nodes, M * R)
+        out[f"{name}/mcpg/vs_good"] = vs_good.numpy().copy()
+        out[f"{name}/mcpg/xs_good"] = xs_good.numpy().copy()
+        out[f"{name}/mcpg/value"] = value.numpy().copy()
+    # ISCO: the reference loader's output for a file that repeats lines (edge_from / edge_to padded with (0, 0))
+    import rlsolver.envs.env_ISCO as env_isco
+    from rlsolver.methods.ISCO import util_maxcut as isco_util
+    path = os.path.join(tmp, "small.txt")
+    params = isco_util.load_data(path)
+    ef, et = params["edge_from"].cpu().long(), params["edge_to"].cpu().long()
+    n = int(params["num_nodes"])
+    out["isco/edge_from"], out["isco/edge_to"], out["isco/num_nodes"] = ef.numpy().copy(), et.numpy().copy(), np.int64(n)
+    B = 8
+    env_isco.BATCH_SIZE = B
+    s = env_isco.ISCO_maxcut({"num_nodes": n, "num_edges": int(ef.shape[0]), "edge_from": ef, "edge_to": et})
+    th.manual_seed(6)
+    x = s.random_gen_init_sample(params)
+    out["isco/x"] = u8(x)
+    for T in (1.0, 0.37):
+        energy, logp = s.get_local_dist(x, th.tensor(T))
+        out[f"isco/T{T}/energy"] = energy.numpy().copy()
+        out[f"isco/T{T}/log_prob"] = logp.numpy().copy()
+    out["names"] = np.array(list(_forms_lists()))
+    save("maxcut_graph_forms", **out)
+
+
+ALL = {"graph_forms": gen_graph_forms, "mcpg_weighted": gen_mcpg_weighted, "isco_steps": gen_isco_steps, "spinsystem_cpu": gen_spinsystem_cpu, "spinsystem": gen_spinsystem, "spinsystem_perenv": gen_spinsystem_perenv, "qubo": gen_qubo, "qubo_asym": gen_qubo_asym, "isco_maxcut": gen_isco_maxcut, "maxcut": gen_maxcut, "sweep": gen_sweep, "lsclass": gen_local_search_class, "ppo": gen_ppo,
        "select": gen_select, "mcpg": gen_mcpg, "tsp": gen_tsp, "tsp_2opt": gen_tsp_2opt, "encoder": gen_encoder,
        "wgain": gen_weighted_gain, "mcpg_glue": gen_mcpg_glue, "evaluator": gen_evaluator, "spinsystem_options": gen_spinsystem_options,
        "api_surface": gen_api_surface, "mcpg_data": gen_mcpg_data,
