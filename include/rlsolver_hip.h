@@ -261,6 +261,23 @@ int rls_maxcut_local_search_supported(const rls_graph* g, int64_t B, int32_t num
  * 0 = element-parallel.  All three give the same result; tests use this to know which one they exercised. */
 int rls_maxcut_node_stats_form(const rls_graph* g, int64_t B, int32_t what);
 
+/* [host] The launch an entry point would make for B envs on this graph: the launchers' own planner, nothing is launched and no
+ * pointer of *g is followed (only tested for NULL) -- what tests pin the launch policy with, without a GPU.  `what`: the entry;
+ * `flags`: the forms of its arguments (0: byte spins and mask on 16-byte-aligned bases, aligned output, the weights' min / max
+ * table present); `cus`: compute units to plan for, <= 0 = the current device's.  Additive (ABI 12). */
+enum { RLS_PLAN_K1 = 0, RLS_PLAN_K5 = 1, RLS_PLAN_K6 = 2, RLS_PLAN_K2 = 3, RLS_PLAN_K3 = 4, RLS_PLAN_WEIGHTS = 5 };
+enum { RLS_PLAN_F32 = 1, RLS_PLAN_BASE_UNALIGNED = 2, RLS_PLAN_MASK_BITS = 4, RLS_PLAN_OUT_UNALIGNED = 8, RLS_PLAN_NO_MINMAX = 16 };
+typedef struct rls_launch_plan {
+    int32_t form;   /* 0 / 1 / 2 / 3: bit tiles of 64 / 32 / 16 / 8 envs per workgroup, 4: one env per wave on byte rows, 5 / 6 / 7: K5's
+                     * batched / single-wave / generic stream forms, 8: lane = env tile (K2 / K3), 9: element-parallel, 10: refused */
+    int32_t waves, planes, vec, wide;   /* template arguments of the kernel: waves per workgroup, counter planes, aligned rows, degrees >= 256 */
+    int32_t stage;                      /* the stage argument the kernel receives */
+    uint32_t grid, block;               /* workgroups, threads per workgroup */
+    int64_t lds;                        /* dynamic LDS bytes */
+    int32_t err;                        /* form 10: the code the entry point returns (RLS_EUNSUPPORTED) */
+} rls_launch_plan;
+int rls_maxcut_launch_plan(const rls_graph* g, int32_t what, int64_t B, int32_t flags, int32_t cus, rls_launch_plan* out);
+
 /* The same local search as separate launches, for graphs rls_maxcut_local_search does not cover (its LDS layout holds
  * two tiles and rd_std: N <= ~7100; these hold one tile: N <= ~15 000 -- and up to N = 39 936 on half tiles of 32 envs
  * (the bare 64-env tile for rows that are not 16-byte multiples, N <= 20 224), through the scratch buffer, which is

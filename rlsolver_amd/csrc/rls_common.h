@@ -2,20 +2,17 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "rlsolver_hip.h"
 #include "rls_host.h"
 
 namespace rls {
 
-constexpr int kWave = 64;                 // CDNA wavefront
-constexpr int kLdsBytes = 160 * 1024;     // per-CU LDS on MI355X
 constexpr int kMaxDynLds = 64 * 1024 * 2; // what we are willing to ask for per workgroup
 
 int check_launch(const char* kernel_name); // hipGetLastError -> RLS_ELAUNCH
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
-inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // ---- counter-based RNG (Philox-4x32-10), keyed by (seed, global env id) so results
 // do not depend on how envs are sharded over ranks/workgroups.
@@ -102,10 +99,18 @@ inline void ensure_dyn_lds(const void* kern, size_t lds) {
     (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);   // table full: as before
 }
 
-inline int grid_for(int64_t total, int block) {
-    int64_t g = ceil_div(total, block);
-    const int64_t cap = 256 * 8 * 4;
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+// Runtime value -> template argument, for the launchers: f is a generic lambda that receives the value as a std::bool_constant /
+// std::integral_constant (V() is a constant expression).  with_bool<false> never instantiates the true form; with_value takes the
+// LAST of its list for a value that is not on it.
+template <bool ALLOW_TRUE = true, typename F>
+inline auto with_bool(bool b, F&& f) {
+    if constexpr (ALLOW_TRUE) { if (b) return f(std::true_type{}); }
+    return f(std::false_type{});
+}
+template <int V0, int... Vs, typename F>
+inline auto with_value(int v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) return f(std::integral_constant<int, V0>{});
+    else return v == V0 ? f(std::integral_constant<int, V0>{}) : with_value<Vs...>(v, f);
 }
 
 inline int check_graph(const rls_graph* g) {

@@ -6,6 +6,15 @@
 #include <atomic>
 
 namespace rls {
+constexpr int kWave = 64;                 // CDNA wavefront
+constexpr int kLdsBytes = 160 * 1024;     // per-CU LDS on MI355X
+inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+inline int grid_for(int64_t total, int block) {
+    int64_t g = ceil_div(total, block);
+    const int64_t cap = 256 * 8 * 4;
+    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+}
+
 int fail(int code, const char* fmt, ...);  // records the message (thread local), returns code
 
 // ---- tuning table --------------------------------------------------------------------------------------------------

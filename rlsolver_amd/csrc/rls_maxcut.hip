@@ -3,14 +3,10 @@
 #include "rls_cutcount.h"
 #include "rls_sweep.h"
 #include "rls_tile32.h"
+#include "rls_maxcut_plan.h"
 #include <cstdlib>
 
 namespace rls {
-
-constexpr int kTileWaves = 4;   // waves cooperating on one 64-env tile (one per SIMD)
-constexpr int kTileWavesMax = 8;   // K1 / K6 take 8 when the tile is so large that only one workgroup fits a CU
-// waves per tile for a bit tile of N nodes: with one workgroup per CU, 4 waves cannot keep enough loads in flight
-static inline int tile_waves_for(int64_t N) { return (size_t)N * 8 + 4 * 4096 + 4096 > 80 * 1024 ? kTileWavesMax : kTileWaves; }
 
 // K1.  One workgroup = one 64-env tile, W waves (4, or 8 for tiles that leave one workgroup per CU): they share
 // the tile load (rls_tile.h: row pieces -> corner turn -> pack -> 64x64 bit transpose; wave w takes every W-th
@@ -198,7 +194,6 @@ __global__ __launch_bounds__(kWave) void k_maxcut_greedy_sweep(uint8_t* __restri
 // wave ~0.9 us of dependent LDS round trips whatever the schedule, so the tile's time is (N / SW) x that:
 // 16 waves when there is at most one tile per CU, otherwise 8 (G22, B = 2^16: 4 waves 1.40, 8 waves 1.68,
 // 16 waves 1.31 x 10^11 candidate flips/s).
-constexpr int kSweepLoadWaves = 4;   // waves that move the tile (the ring holds 4 row-piece stages)
 
 template <bool VEC, int SW>
 __global__ __launch_bounds__(SW * kWave) void k_maxcut_greedy_sweep_batched(
@@ -291,7 +286,6 @@ __global__ __launch_bounds__(SW * kWave) void k_maxcut_greedy_sweep_levels32(
 // graphs past the half tile, N > ~40 000 up to ~80 000 / ~160 000 nodes, which ran ONE ENV PER WAVE on a byte row until round 5
 // (K5 120 ms, local_search_inplace 158 ms for 4096 envs at N = 44 000 against 0.4 / 2.5 ms at N = 39 936).  Same steps, same
 // schedules, same counters as the half-tile kernels; 8 waves per workgroup.
-constexpr int kNarrowWaves = 8;
 template <typename WT> __host__ __device__ constexpr size_t narrow_words_bytes(int64_t N) { return (((size_t)(N + 2) * sizeof(WT)) + 15) & ~(size_t)15; }
 
 template <typename T, bool VEC, int P, typename WT>
@@ -590,7 +584,6 @@ __global__ __launch_bounds__(kTileWaves * kWave) void k_node_stats_tile(const ui
 // the four bytes of a dword) and every env's 64 consecutive results leave as ONE 256-byte store (the lane = env
 // form wrote 16 bytes per lane into 64 different rows).  out = cutdeg (int64) | deg - 2c (int32) | deg - mult c.
 // =====================================================================================
-constexpr int kNsWaves = 8;
 
 template <int NP>
 __device__ __forceinline__ uint32_t ns_extract4(const uint64_t (&pl)[8], int half, int r) {
@@ -1198,178 +1191,6 @@ __global__ __launch_bounds__(kNsWaves * kWave) void k_node_stats_bits32(const ui
     }
 }
 
-static inline size_t node_stats_bits32_lds(int64_t N, bool with_stage) {
-    return (((size_t)N * 4 + 15) & ~(size_t)15) + (with_stage ? (size_t)kNsWaves * kStageBytes : 0);
-}
-static inline size_t node_stats_bits_lds(int64_t N, bool with_stage = true, int waves = kNsWaves) {
-    return (((size_t)N * 8 + 15) & ~(size_t)15) + (with_stage ? (size_t)waves * kStageBytes : 0);
-}
-// the bit-sliced kernel needs the slabs, an unweighted graph, byte-sized counters and a tile that fits.  A tile costs about
-// 0.011 us per node however few envs it holds, the element-parallel kernels about 2e-6 us per (env, node + entry): K3 on a
-// G22-sized graph 28 us flat vs 9 / 21 / 68 us at 64 / 256 / 1024 envs, N = 10^4 with 10^4 edges 88 flat vs 7 / 17 / 70
-// (tools/sweeps/node_stats_forms.py) -- so small batches go element-parallel
-static inline bool node_stats_batch_fills_tiles(const rls_graph* g, int64_t B) {
-    const int64_t force = (int64_t)knob(KN_NODE_STATS_MIN_B, -1);   // dev knob
-    if (force >= 0) return B >= force;
-    return (double)B * (double)(g->num_nodes + g->nnz) > 4000.0 * (double)g->num_nodes;
-}
-static inline bool node_stats_use_bits(const rls_graph* g, const int32_t* ell_ptr, const int32_t* ell, int64_t B) {
-    const bool off = knob_on(KN_NODE_STATS_LANE_ENV);   // dev knob: the lane = env kernels
-    return !off && ell_ptr && ell && !g->wgt && g->max_degree < 65536 && node_stats_batch_fills_tiles(g, B) &&
-           (knob(KN_NARROW_TILE, 1) != 0 ? narrow_words_bytes<uint8_t>(g->num_nodes)     // (half tiles without the row-piece stage if
-                                         : node_stats_bits32_lds(g->num_nodes, false)) <= (size_t)kLdsBytes;   // need be, narrow ones past them)
-}
-template <int MODE, typename WT = int32_t>
-static int launch_node_stats_bits(const rls_graph* g, const uint8_t* x, int64_t B, const int32_t* rowptr,
-                                  const int32_t* ell_ptr, const int32_t* ell, int mult, void* out, void* stream,
-                                  int32_t* minmax = nullptr, int64_t out_pitch = 0) {
-    const int64_t N = g->num_nodes;
-    const bool vec = tile_rows_aligned(x, N, 1);
-    const bool wide = g->max_degree >= 256;
-    const int knob32 = (int)knob(KN_NS_TILE32, -1);   // dev knob: half tiles at any size
-    // Half tiles: past the 64-env tile; and, for byte rows of 16-byte multiples whose half tile has room for its stage, where they
-    // measure faster (this round's GPU runs): batches of few tiles -- a tile costs the same however few envs it holds, so twice
-    // as many half as long workgroups win while CUs are idle: K3 / K2 up to 8192 envs (G22-sized 4096: 31 -> 23 us, BA n = 10^4
-    // 135 -> 101, G70-sized 88 -> 62), the weights pre-pass up to 2048 (its 64-env kernel has the dword stores) --, K3 on short
-    // rows at full batches (G22-sized 2^16: 166 -> 154 us), and -- few tiles again -- rows whose 64-env tile has no room for its
-    // stage (N > ~15 800: K3 at N = 20 000, 4096 envs 278 -> 186 us)
-    const int64_t t64 = ceil_div(B, kWave);
-    const bool few = MODE == 2 ? 8 * t64 <= (int64_t)num_cus() : 2 * t64 <= (int64_t)num_cus();
-    // (round 6: from two 64-env tiles per CU on -- N = 3008, 2^15 envs: 121 us on 64-env tiles, 109-112 on half tiles)
-    const bool full_k3 = MODE == 1 && t64 >= 2 * (int64_t)num_cus() && (size_t)N * 8 <= 64 * 1024;
-    const bool prefer32 = knob32 < 0 && vec && (N & 7) == 0 && node_stats_bits32_lds(N, true) <= (size_t)kLdsBytes &&
-                          (few || full_k3 || (node_stats_bits_lds(N, true) > (size_t)kLdsBytes && 2 * t64 <= (int64_t)num_cus()));
-    // Narrow tiles (16 / 8 envs, rls_tile32.h) where the half tile is past the LDS (N > 40 960): the rows these took before went
-    // element-parallel -- one L2 gather per (env, entry)
-    // -- and, like K1 / K6 / K5 (narrow_policy), for batches of few tiles on rows the narrow loader's fast path takes: a tile's load,
-    // count and stores are one chain whatever it holds, so 256 CUs want 256+ tiles (tools/timing/narrow_ns_ab.py, K3 / K2 / weights in us,
-    // wide -> narrow: N = 10^4, 4096 envs 62 / 83 / 95 -> 44 / 74 / 91 (16 envs); N = 20 000, 1024 envs 128 / 102 / 148 -> 75 / 55 / 114
-    // (8 envs); G22-sized, 256 envs 18.4 / 15.3 / 25.5 -> 11.9 / 9.5 / 22.5).  The weights' 8-env tiles only up to 512 envs (every tile
-    // folds its min / max into the table with atomics: G22-sized 1024 envs 27.8 -> 32.6)
-    const int64_t nk = knob(KN_NARROW_TILE, 1);
-    int auto_n = 0;
-    if (nk == 1 && knob32 < 0 && vec && (N & 7) == 0) {
-        const int64_t cus = num_cus();
-        if (MODE == 2) {    // (G22-sized, 4096 envs on 16-env tiles: 31 -> 57 us -- 256 tiles' worth of min / max atomics per node)
-            if (ceil_div(B, 8) <= cus / 4) auto_n = 8;
-            else if (N >= 8192 && ceil_div(B, 16) <= cus / 4) auto_n = 16;
-        } else {
-            if (ceil_div(B, 8) <= cus) auto_n = 8;
-            else if (ceil_div(B, 16) <= cus) auto_n = 16;
-        }
-    }
-    if (nk != 0 && (nk >= 2 || auto_n || node_stats_bits32_lds(N, false) > (size_t)kLdsBytes)) {
-        const size_t l16 = narrow_words_bytes<uint16_t>(N), l8 = narrow_words_bytes<uint8_t>(N);
-        const bool w16 = nk != 3 && auto_n != 8 && l16 <= (size_t)kLdsBytes;
-        const size_t ln = w16 ? l16 : l8;
-        const dim3 gn((unsigned)ceil_div(B, (int64_t)(w16 ? 16 : 8))), bn(kNsWaves * kWave);
-#define RLS_NSN_LAUNCH(VEC, WIDE)                                                                                    \
-    do {                                                                                                            \
-        if (w16) { auto kern = k_node_stats_bits32<MODE, VEC, WIDE, WT, uint16_t>; ensure_dyn_lds((const void*)kern, ln);   \
-                   hipLaunchKernelGGL(kern, gn, bn, ln, as_stream(stream), x, B, N, rowptr, ell_ptr, ell, mult, out, minmax, \
-                                      out_pitch > 0 ? out_pitch : N, 0); }                                          \
-        else     { auto kern = k_node_stats_bits32<MODE, VEC, WIDE, WT, uint8_t>; ensure_dyn_lds((const void*)kern, ln);    \
-                   hipLaunchKernelGGL(kern, gn, bn, ln, as_stream(stream), x, B, N, rowptr, ell_ptr, ell, mult, out, minmax, \
-                                      out_pitch > 0 ? out_pitch : N, 0); }                                          \
-    } while (0)
-        if (wide) { if (vec) RLS_NSN_LAUNCH(true, true); else RLS_NSN_LAUNCH(false, true); }
-        else      { if (vec) RLS_NSN_LAUNCH(true, false); else RLS_NSN_LAUNCH(false, false); }
-#undef RLS_NSN_LAUNCH
-        return check_launch("k_node_stats_bits32<narrow>");
-    }
-    if (knob32 > 0 || prefer32 || node_stats_bits_lds(N, false) > (size_t)kLdsBytes) {   // half tiles (rls_tile32.h)
-        int st32 = (vec && (N & 7) == 0 && node_stats_bits32_lds(N, true) <= (size_t)kLdsBytes) ? 1 : 0;
-        size_t l32 = node_stats_bits32_lds(N, st32 != 0);
-        {   // K3's row staging on full half tiles (the kernel's comment): 16-byte-aligned output, rows of 4-node multiples
-            const int rk = (int)knob(KN_NS_ROWS, -1);
-            const size_t lrows = node_stats_bits32_lds(N, false) + (size_t)kNsWaves * kHalf * 132;
-            // measured (tools/timing/k3_rows.py, half tiles per group -> rows): N = 3008 112 -> 109 us, G70-sized 1603 -> 1527, BA n = 10^4
-            // 1093 -> 1043; G22-sized 162 -> 167 (sixteen 512-byte pieces per pair are too few stores to pay for the staging): from 3000 nodes
-            if (MODE == 1 && st32 && (N & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 && (rk < 0 ? N >= 3000 : rk != 0) &&
-                lrows <= (size_t)kLdsBytes) {
-                st32 |= 4;
-                if (lrows > l32) l32 = lrows;
-            }
-        }
-        const dim3 g32((unsigned)ceil_div(B, (int64_t)kHalf)), b32(kNsWaves * kWave);
-#define RLS_NS32_LAUNCH(KERN)                                                                                        \
-    do {                                                                                                            \
-        auto kern = KERN;                                                                                           \
-        if (l32 > 64 * 1024) ensure_dyn_lds((const void*)kern, l32); \
-        hipLaunchKernelGGL(kern, g32, b32, l32, as_stream(stream), x, B, N, rowptr, ell_ptr, ell, mult, out, minmax,  \
-                           out_pitch > 0 ? out_pitch : N, st32);                                                     \
-    } while (0)
-        if (wide) {
-            if (vec) RLS_NS32_LAUNCH((k_node_stats_bits32<MODE, true, true, WT>));
-            else RLS_NS32_LAUNCH((k_node_stats_bits32<MODE, false, true, WT>));
-        } else {
-            if (vec) RLS_NS32_LAUNCH((k_node_stats_bits32<MODE, true, false, WT>));
-            else RLS_NS32_LAUNCH((k_node_stats_bits32<MODE, false, false, WT>));
-        }
-#undef RLS_NS32_LAUNCH
-        return check_launch("k_node_stats_bits32");
-    }
-    const int has_stage = node_stats_bits_lds(N, true) <= (size_t)kLdsBytes ? 1 : 0;
-    // 8 waves per tile, or 4 where that turns a launch of one-and-a-bit rounds of workgroups into ONE round: a G22-sized tile
-    // is 16 KB + 4 KB of row-piece stage per wave -- 3 eight-wave workgroups per CU (768 resident: 1024 tiles = a full round
-    // and a third of one), 5 four-wave ones (every tile resident at once)
-    const int force_w = (int)knob(KN_NS_WAVES, 0);     // dev knob
-    const int64_t tiles = ceil_div(B, kWave);
-    auto resident = [&](int wv) {
-        const int64_t by_lds = (int64_t)((size_t)kLdsBytes / node_stats_bits_lds(N, has_stage != 0, wv)), by_waves = 32 / wv;
-        return (int64_t)num_cus() * (by_lds < by_waves ? by_lds : by_waves);
-    };
-    // measured (tools/timing/k7_packed.py, ls_parts.py with RLS_NS_WAVES=4 | 8; G22 2^16): K3 171 vs 167 us, weights 156 vs 139 us,
-    // G70 2^17 K3 1889 vs 1656 -- the single round does not pay for halving a tile's waves: 8 stays, 4 is a knob
-    (void)resident;
-    const bool four = force_w == 4 && !wide && has_stage;
-    const int waves = four ? 4 : kNsWaves;
-    size_t lds = node_stats_bits_lds(N, has_stage != 0, waves);
-    // MODE 2's parked min / max folds (the kernel's comment): 4 N bytes behind the tile, over the stages' bytes -- where they fit
-    // without costing the CU a workgroup
-    int stage_flags = has_stage;
-    const int seeds = (int)knob(KN_NS_PARK, 16);       // dev knob: 0 = every tile folds as it goes
-    if (MODE == 2 && minmax && seeds > 0 && tiles > seeds) {
-        const size_t with_stash = node_stats_bits_lds(N, false, waves) + (size_t)N * 4;
-        const size_t need = with_stash > lds ? with_stash : lds;
-        if (need <= (size_t)kLdsBytes && (size_t)kLdsBytes / need == (size_t)kLdsBytes / lds) { lds = need; stage_flags |= 2 | (seeds << 8); }
-    }
-    // K2 / K3 of full tiles through row staging (the kernel's comment): 16-byte-aligned output rows of 4-node multiples, 8 KB + of
-    // LDS per wave behind the tile (where the row-piece stages are: the hub groups' cooperative pass needs those)
-    const int rows_knob = (int)knob(KN_NS_ROWS, -1);
-    const size_t lds_rows = node_stats_bits_lds(N, false, waves) + (size_t)kNsWaves * kWave * 132;
-    // measured (tools/timing/k3_rows.py, per group -> rows): K3 G70-sized 2^17 1648 -> 1574 us, BA n = 10^4 2^16 1136 -> 1032; G22-sized
-    // 2^16 169 -> 178 and N = 3008 117 -> 123 (the 64 KB of staging cost the CU a workgroup there); K2's int64 rows lose everywhere
-    // (G70 2274 -> 2361): K3, on tiles that leave one workgroup per CU either way
-    const bool rows_auto = MODE == 1 && 2 * node_stats_bits_lds(N, true, waves) > (size_t)kLdsBytes;
-    if (MODE != 2 && waves == kNsWaves && has_stage && (N & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 &&
-        (rows_knob < 0 ? rows_auto : rows_knob != 0) && lds_rows <= (size_t)kLdsBytes) {
-        stage_flags |= 4;
-        if (lds_rows > lds) lds = lds_rows;
-    }
-    const dim3 grid((unsigned)tiles), block(waves * kWave);
-#define RLS_NS_LAUNCH(KERN)                                                                                         \
-    do {                                                                                                            \
-        auto kern = KERN;                                                                                           \
-        if (lds > 64 * 1024)                                                                                        \
-            ensure_dyn_lds((const void*)kern, lds);     \
-        hipLaunchKernelGGL(kern, grid, block, lds, as_stream(stream), x, B, N, rowptr, ell_ptr, ell, mult, out, minmax, \
-                           out_pitch > 0 ? out_pitch : N, stage_flags);                                             \
-    } while (0)
-    if (four) {
-        if (vec) RLS_NS_LAUNCH((k_node_stats_bits<MODE, true, false, WT, 4>));
-        else RLS_NS_LAUNCH((k_node_stats_bits<MODE, false, false, WT, 4>));
-    } else if (wide) {
-        if (vec) RLS_NS_LAUNCH((k_node_stats_bits<MODE, true, true, WT>));
-        else RLS_NS_LAUNCH((k_node_stats_bits<MODE, false, true, WT>));
-    } else {
-        if (vec) RLS_NS_LAUNCH((k_node_stats_bits<MODE, true, false, WT>));
-        else RLS_NS_LAUNCH((k_node_stats_bits<MODE, false, false, WT>));
-    }
-#undef RLS_NS_LAUNCH
-    return check_launch("k_node_stats_bits");
-}
-
 
 // one wave per row
 __global__ __launch_bounds__(256) void k_select_better_rows(uint8_t* __restrict__ xs0, int64_t* __restrict__ vs0,
@@ -1678,131 +1499,44 @@ __global__ __launch_bounds__(256) void k_maxcut_greedy_sweep_rows(uint8_t* __res
     if (lane == 0) obj[b] += gain_total;
 }
 
-static inline int rows_waves(int64_t N) {   // waves (= envs) per workgroup of a row kernel, 0 when even one row does not fit
-    const size_t per = ((size_t)N + 15) & ~(size_t)15;
-    if (per > (size_t)kLdsBytes) return 0;
-    int w = (int)((size_t)kLdsBytes / per);
-    return w > 4 ? 4 : w;
-}
-
 }  // namespace rls
 
 using namespace rls;
 
-// ---- narrow-tile launches (16 or 8 envs per workgroup: rls_tile32.h).  `want`: 0 = the widest that fits, 16 / 8 = that one.
-// kNarrowNo: not applicable here (nothing was launched, no error recorded).
-constexpr int kNarrowNo = 1;
-// Which tile a launch of B envs should take when several fit: a tile's load / sweep / store is a chain of its own whatever it holds,
-// so a batch of few tiles wants NARROWER ones until the chip is full -- 4096 envs are 64 / 128 / 256 / 512 tiles of 64 / 32 / 16 / 8
-// envs on 256 CUs.  Returns 0 (the wide tiles), 16 or 8.  RLS_NARROW_TILE: 0 never, 1 automatic, 2 / 3 force 16 / 8 where they fit.
-static int narrow_policy(int64_t N, int64_t B, bool rows_vec, Knob wide_knob) {
-    const int64_t k = knob(KN_NARROW_TILE, 1);
-    if (k == 0 || (k == 1 && knob(wide_knob, -1) >= 0)) return 0;      // (a forced 64-env / half-tile form is honoured)
-    if (k == 2) return 16;
-    if (k == 3) return 8;
-    // automatic (tools/timing/narrow_policy.py, K1 / K6 / K5 in us, wide -> narrow): N = 10^4, 4096 envs 21.8 / 31.6 / 47.6 -> 11.7 /
-    // 22.4 / 39.2 (16 envs), 256 envs 19.4 / 27.8 / 42.4 -> 7.6 / 13.2 / 24.9 (8 envs); N = 39 936, 4096 envs 47 / 120 / 356 -> 36 / 86 /
-    // 135; N = 2000, 4096 envs 10.4 / 11.6 / 47 -> 7.1 / 9.1 / 46; N = 800: nothing.  From 16 384 envs on the wide tiles win
-    // (N = 10^4: 29.7 / 77.5 / 69.8 vs 32.8 / 89.6 / 110) -- the chip is full and a narrow tile walks the edge list / schedule per 16 envs.
-    if (!rows_vec || (N & 7) != 0 || N < 1536) return 0;      // (the narrow loader's fast path: byte rows of 16- or 8-byte multiples)
-    const int64_t cus = num_cus();
-    if (ceil_div(B, 8) <= cus) return 8;
-    if (ceil_div(B, 16) <= cus) return 16;
-    return 0;
+static_assert(kPlanStageBytes == kStageBytes && kPlanHalf == kHalf && kPlanRing == kRing && kPlanSweepMaxDeg == kSweepMaxDeg,
+              "rls_maxcut_plan.h restates constants of the kernels' headers");
+static_assert(narrow_words_bytes<uint16_t>(1001) == tile_lds(1001 + 2, 2, 0) && narrow_words_bytes<uint8_t>(1001) == tile_lds(1001 + 2, 1, 0),
+              "the planner's narrow tile is the kernels'");
+
+// ---- from a plan to a launch ---------------------------------------------------------------------------------------------
+// The shape the planners see.  `rows_aligned`: tile_rows_aligned of the spin rows (and of K6's byte mask); `ell`: the slabs of the
+// adjacency the entry reads (node stats); `out` / `minmax`: the node stats' outputs.
+static TileShape shape_of(const rls_graph* g, int64_t B, bool rows_aligned, int spin_bytes = 1, bool mask_bits = false,
+                          bool has_ell = false, const void* out = nullptr, const void* minmax = nullptr, int cus = 0) {
+    TileShape s{};
+    s.N = g->num_nodes; s.B = B; s.E = g->num_stored_edges; s.G = g->num_sweep_groups; s.nnz = g->nnz;
+    s.spin_bytes = spin_bytes;
+    s.rows_aligned = rows_aligned;
+    s.out16 = (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+    s.mask_bits = mask_bits; s.minmax = minmax != nullptr; s.weighted = g->wgt != nullptr;
+    s.max_degree = g->max_degree;
+    s.has_levels = g->sweep_lv_ptr && g->sweep_lv_data;
+    s.has_batches = g->sweep_rowptr && g->sweep_stream;
+    s.has_ell = has_ell;
+    s.col4 = (((uintptr_t)g->col) & 3) == 0;
+    s.cus = cus > 0 ? cus : num_cus();
+    return s;
 }
 
-static int launch_obj_narrow(const rls_graph* g, const void* x, int spin_bytes, int64_t B, int64_t* obj, int want, void* stream) {
-    const int64_t N = g->num_nodes, E = g->num_stored_edges;
-    const int Pn = pick_planes(E) == 12 ? 16 : pick_planes(E);
-    const bool vecn = tile_rows_aligned(x, N, spin_bytes);
-    const int hv = g->if_bidirectional ? 1 : 0;
-    const size_t l16 = narrow_words_bytes<uint16_t>(N) + (size_t)kNarrowWaves * kWave * 8, l8 = narrow_words_bytes<uint8_t>(N) + (size_t)kNarrowWaves * kWave * 8;
-    if (Pn == 0 || l8 > (size_t)kLdsBytes) return kNarrowNo;
-    const bool w16 = want != 8 && l16 <= (size_t)kLdsBytes;
-    const size_t ln = w16 ? l16 : l8;
-    const dim3 gn((unsigned)ceil_div(B, (int64_t)(w16 ? 16 : 8))), bn(kNarrowWaves * kWave);
-#define LAUNCH_OBJN(T, VEC, PP)                                                                                         \
-    do {                                                                                                                \
-        if (w16) { auto kern = k_maxcut_obj_n<T, VEC, PP, uint16_t>; ensure_dyn_lds((const void*)kern, ln);             \
-                   hipLaunchKernelGGL(kern, gn, bn, ln, as_stream(stream), (const T*)x, B, N, g->eu, g->ev, E, hv, obj); } \
-        else     { auto kern = k_maxcut_obj_n<T, VEC, PP, uint8_t>; ensure_dyn_lds((const void*)kern, ln);              \
-                   hipLaunchKernelGGL(kern, gn, bn, ln, as_stream(stream), (const T*)x, B, N, g->eu, g->ev, E, hv, obj); } \
-    } while (0)
-#define DISPATCH_PN(T, VEC)                        \
-    switch (Pn) {                                  \
-        case 16: LAUNCH_OBJN(T, VEC, 16); break;   \
-        case 20: LAUNCH_OBJN(T, VEC, 20); break;   \
-        default: LAUNCH_OBJN(T, VEC, 24); break;   \
-    }
-    if (spin_bytes == 1) { if (vecn) { DISPATCH_PN(uint8_t, true) } else { DISPATCH_PN(uint8_t, false) } }
-    else { DISPATCH_PN(float, false) }
-#undef DISPATCH_PN
-#undef LAUNCH_OBJN
-    return check_launch("k_maxcut_obj_n");
+template <typename... KA, typename... A>
+static int launch(void (*kern)(KA...), const char* name, const LaunchPlan& p, void* stream, A... args) {
+    ensure_dyn_lds((const void*)kern, p.lds);
+    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.block), p.lds, as_stream(stream), static_cast<KA>(args)...);
+    return check_launch(name);
 }
-
-static int launch_propose_accept_narrow(const rls_graph* g, uint8_t* x, int64_t B, const uint8_t* mask, int32_t mask_bits, int64_t* obj, int want,
-                                        void* stream) {
-    const int64_t N = g->num_nodes, E = g->num_stored_edges;
-    const int Pn = pick_planes(E) == 12 ? 16 : pick_planes(E);
-    const bool vecn = tile_rows_aligned(x, N, 1) && (mask_bits || tile_rows_aligned(mask, N, 1));
-    const int hv = g->if_bidirectional ? 1 : 0;
-    const size_t l16 = narrow_words_bytes<uint16_t>(N) + (size_t)kNarrowWaves * kWave * 8, l8 = narrow_words_bytes<uint8_t>(N) + (size_t)kNarrowWaves * kWave * 8;
-    if (Pn == 0 || l8 > (size_t)kLdsBytes) return kNarrowNo;
-    const bool w16 = want != 8 && l16 <= (size_t)kLdsBytes;
-    const size_t ln = w16 ? l16 : l8;
-    const dim3 gn((unsigned)ceil_div(B, (int64_t)(w16 ? 16 : 8))), bn(kNarrowWaves * kWave);
-#define LAUNCH_PAN(VEC, PP, MB)                                                                                          \
-    do {                                                                                                                \
-        if (w16) { auto kern = k_maxcut_propose_accept_n<VEC, PP, uint16_t, MB>; ensure_dyn_lds((const void*)kern, ln); \
-                   hipLaunchKernelGGL(kern, gn, bn, ln, as_stream(stream), x, mask, B, N, g->eu, g->ev, E, hv, obj); }  \
-        else     { auto kern = k_maxcut_propose_accept_n<VEC, PP, uint8_t, MB>; ensure_dyn_lds((const void*)kern, ln);  \
-                   hipLaunchKernelGGL(kern, gn, bn, ln, as_stream(stream), x, mask, B, N, g->eu, g->ev, E, hv, obj); }  \
-    } while (0)
-#define DISPATCH_PN(VEC, MB)                       \
-    switch (Pn) {                                  \
-        case 16: LAUNCH_PAN(VEC, 16, MB); break;   \
-        case 20: LAUNCH_PAN(VEC, 20, MB); break;   \
-        default: LAUNCH_PAN(VEC, 24, MB); break;   \
-    }
-    if (mask_bits) { if (vecn) { DISPATCH_PN(true, true) } else { DISPATCH_PN(false, true) } }
-    else { if (vecn) { DISPATCH_PN(true, false) } else { DISPATCH_PN(false, false) } }
-#undef DISPATCH_PN
-#undef LAUNCH_PAN
-    return check_launch("k_maxcut_propose_accept_n");
-}
-
-static int launch_sweep_narrow(const rls_graph* g, uint8_t* x, int64_t B, int64_t* obj, int want, void* stream) {
-    const int64_t N = g->num_nodes, E = g->num_stored_edges, G = g->num_sweep_groups;
-    if (g->wgt || !g->sweep_lv_ptr || !g->sweep_lv_data || G <= 0 || knob_on(KN_SWEEP_NO_LEVELS)) return kNarrowNo;
-    const int Pn = pick_planes(E) == 12 ? 16 : pick_planes(E);
-    const bool vec = tile_rows_aligned(x, N, 1);
-    auto ldsn_of = [&](size_t wb) { return wb + (((size_t)(G + 1) * 4 + 15) & ~(size_t)15) + (size_t)kNarrowWaves * kWave * 8; };
-    const size_t l16 = ldsn_of(narrow_words_bytes<uint16_t>(N)), l8 = ldsn_of(narrow_words_bytes<uint8_t>(N));
-    if (Pn == 0 || l8 > (size_t)kLdsBytes) return kNarrowNo;
-    const bool w16 = want != 8 && l16 <= (size_t)kLdsBytes;
-    const size_t ln = w16 ? l16 : l8;
-    const dim3 gn((unsigned)ceil_div(B, (int64_t)(w16 ? 16 : 8))), bn(kNarrowWaves * kWave);
-    const int hv = g->if_bidirectional ? 1 : 0;
-    hipStream_t s = as_stream(stream);
-#define LAUNCH_SWLN(VEC, PP)                                                                                                       \
-    do {                                                                                                                           \
-        if (w16) { auto kern = k_maxcut_greedy_sweep_levels_n<VEC, PP, uint16_t>; ensure_dyn_lds((const void*)kern, ln);           \
-                   hipLaunchKernelGGL(kern, gn, bn, ln, s, x, B, N, g->sweep_lv_ptr, g->sweep_lv_data, G, g->eu, g->ev, E, hv, obj); } \
-        else     { auto kern = k_maxcut_greedy_sweep_levels_n<VEC, PP, uint8_t>; ensure_dyn_lds((const void*)kern, ln);            \
-                   hipLaunchKernelGGL(kern, gn, bn, ln, s, x, B, N, g->sweep_lv_ptr, g->sweep_lv_data, G, g->eu, g->ev, E, hv, obj); } \
-    } while (0)
-#define DISPATCH_SWLN(VEC)                        \
-    switch (Pn) {                                 \
-        case 16: LAUNCH_SWLN(VEC, 16); break;     \
-        case 20: LAUNCH_SWLN(VEC, 20); break;     \
-        default: LAUNCH_SWLN(VEC, 24); break;     \
-    }
-    if (vec) { DISPATCH_SWLN(true) } else { DISPATCH_SWLN(false) }
-#undef DISPATCH_SWLN
-#undef LAUNCH_SWLN
-    return check_launch("k_maxcut_greedy_sweep_levels_n");
-}
+static int refuse(const LaunchPlan& p) { return fail(p.err, "%s", p.msg); }
+// a narrow plan's word type (16 / 8 envs per workgroup) as a type
+template <typename F> static int with_narrow_word(const LaunchPlan& p, F&& f) { return p.form == PF_NARROW16 ? f(uint16_t{}) : f(uint8_t{}); }
 
 extern "C" {
 
@@ -1827,115 +1561,27 @@ int rls_maxcut_obj(const rls_graph* g, const void* x, int spin_bytes, int64_t B,
     RLS_REQUIRE(x && obj, RLS_EINVAL, "x/obj is NULL");
     RLS_REQUIRE(spin_bytes == 1 || spin_bytes == 4, RLS_EINVAL, "spin_bytes must be 1 or 4");
     const int64_t N = g->num_nodes, E = g->num_stored_edges;
-    if (const int nw = narrow_policy(N, B, tile_rows_aligned(x, N, spin_bytes), KN_K1_TILE32))
-        if (const int rc = launch_obj_narrow(g, x, spin_bytes, B, obj, nw, stream); rc != kNarrowNo) return rc;
-    int tw = tile_waves_for(N);
-    size_t lds = (size_t)N * 8 + (size_t)tw * kWave * 8;
-    if (lds > (size_t)kLdsBytes && (size_t)N * 8 + (size_t)kTileWaves * kWave * 8 <= (size_t)kLdsBytes) {
-        // the tile alone still fits (N <= 20 224: Gset's 20 000-node G81): 4 waves, no row-piece stage (lane-per-env loads at
-        // ~2.5 TB/s) -- an order of magnitude ahead of the one-env-per-wave form below
-        tw = kTileWaves;
-        lds = (size_t)N * 8 + (size_t)tw * kWave * 8;
-    }
-    // Half tiles (32 envs, 32-bit words: rls_tile32.h).  Where the 64-env tile does not fit but N * 4 bytes do (20 224 < N <=
-    // 40 448) -- and, for byte rows of 16-byte multiples (their fast loader), where they measure faster (tools/timing/k1_tile32.py):
-    // rows past 8192 nodes, whose 64-env tile leaves one workgroup per CU or no room for the row-piece stage (G70-sized 2^17:
-    // 280 -> 262 us, N = 20 000 2^16: 374 -> 282), and launches of at most two 64-env tiles per CU (G22-sized 2^14: 14.8 -> 13.4 us;
-    // at 2^16 the half tiles LOSE, 34.4 -> 36.3: twice the edge-list reads per env).  Dev knob RLS_K1_TILE32 = 0 | 1 forces the choice.
-    const int knob32 = (int)knob(KN_K1_TILE32, -1);
-    {
-        auto lds32 = [&](int ww) { return (((size_t)N * 4 + 15) & ~(size_t)15) + (size_t)ww * kWave * 8; };
-        // 8 waves once two 4-wave workgroups (with their stages) no longer share a CU: one 4-wave workgroup per CU cannot keep
-        // enough loads in flight (N = 15 984 .. 16 384 ran at 0.43 of HBM beside 0.61 at 15 872, where two still fit)
-        int w32 = 2 * (lds32(kTileWaves) + (size_t)kTileWaves * kStageBytes) > (size_t)kLdsBytes ? kTileWavesMax : kTileWaves;
-        if (lds32(w32) > (size_t)kLdsBytes) w32 = kTileWaves;
-        size_t l32 = lds32(w32);
-        const int P32 = pick_planes(E);
-        const bool vec = tile_rows_aligned(x, N, spin_bytes);
-        const bool fast32 = spin_bytes == 1 && vec && (N & 7) == 0;      // (rows of 16- or 8-byte multiples: rls_tile32.h)
-        const bool want32 = knob32 >= 0 ? knob32 != 0
-                                        : fast32 && (N >= 3000 || ceil_div(B, kWave) <= 2 * (int64_t)num_cus());
-        // (N >= 3000, round 5: until then "rows past 8192 nodes" -- at 2^16 envs the half tile also wins from 3000 nodes on, K1 N = 3008 /
-        // 5008 / 7008: 42.6 / 77.5 / 103.8 -> 38.6 / 75.1 / 102.2 us, rows of 8-byte multiples 49.8 / 89.4 / 124.0 -> 43.1 / 83.1 / 116.3;
-        // at G22's 2000 it loses, 36.3 vs 34.4: tools/sweeps/align_sweep.py with RLS_K1_TILE32 = 1)
-        if ((want32 || lds > (size_t)kLdsBytes) && l32 <= (size_t)kLdsBytes && P32 != 0) {
-            const int st_off = tile_stage_offset(&l32, w32, spin_bytes == 1 && vec && (N & 7) == 0);
-            const dim3 g32((unsigned)ceil_div(B, (int64_t)kHalf)), b32(w32 * kWave);
-            const int hv = g->if_bidirectional ? 1 : 0;
-            hipStream_t s32 = as_stream(stream);
-#define LAUNCH_OBJ32(T, VEC, PP)                                                                                        \
-    do {                                                                                                                \
-        auto kern = w32 == kTileWavesMax ? k_maxcut_obj32<T, VEC, PP, kTileWavesMax> : k_maxcut_obj32<T, VEC, PP, kTileWaves>; \
-        if (l32 > 64 * 1024) ensure_dyn_lds((const void*)kern, l32); \
-        hipLaunchKernelGGL(kern, g32, b32, l32, s32, (const T*)x, B, N, g->eu, g->ev, E, hv, obj, st_off);              \
-    } while (0)
-#define DISPATCH_P32(T, VEC)                        \
-    switch (P32) {                                  \
-        case 12: LAUNCH_OBJ32(T, VEC, 12); break;   \
-        case 16: LAUNCH_OBJ32(T, VEC, 16); break;   \
-        case 20: LAUNCH_OBJ32(T, VEC, 20); break;   \
-        default: LAUNCH_OBJ32(T, VEC, 24); break;   \
-    }
-            if (spin_bytes == 1) {
-                if (vec) { DISPATCH_P32(uint8_t, true) } else { DISPATCH_P32(uint8_t, false) }
-            } else {
-                DISPATCH_P32(float, false)
-            }
-#undef DISPATCH_P32
-#undef LAUNCH_OBJ32
-            return check_launch("k_maxcut_obj32");
+    const int hv = g->if_bidirectional ? 1 : 0;
+    const LaunchPlan p = plan_obj(shape_of(g, B, tile_rows_aligned(x, N, spin_bytes), spin_bytes));
+    auto typed = [&](auto t) {   // T: the spins' type.  Float rows have the 64-env tile's VEC form only
+        using T = decltype(t);
+        constexpr bool kBytes = std::is_same<T, uint8_t>::value;
+        const T* xs = static_cast<const T*>(x);
+        switch (p.form) {
+            case PF_TILE64:
+                return with_bool(p.vec, [&](auto V) { return with_value<12, 16, 20, 24>(p.planes, [&](auto P) { return with_value<kTileWavesMax, kTileWaves>(p.waves, [&](auto W) {
+                    return launch(k_maxcut_obj<T, V(), P(), W()>, "k_maxcut_obj", p, stream, xs, B, N, g->eu, g->ev, E, hv, obj, p.stage); }); }); });
+            case PF_TILE32:
+                return with_bool<kBytes>(p.vec, [&](auto V) { return with_value<12, 16, 20, 24>(p.planes, [&](auto P) { return with_value<kTileWavesMax, kTileWaves>(p.waves, [&](auto W) {
+                    return launch(k_maxcut_obj32<T, V(), P(), W()>, "k_maxcut_obj32", p, stream, xs, B, N, g->eu, g->ev, E, hv, obj, p.stage); }); }); });
+            case PF_NARROW16: case PF_NARROW8:
+                return with_bool<kBytes>(p.vec, [&](auto V) { return with_value<16, 20, 24>(p.planes, [&](auto P) { return with_narrow_word(p, [&](auto w) {
+                    return launch(k_maxcut_obj_n<T, V(), P(), decltype(w)>, "k_maxcut_obj_n", p, stream, xs, B, N, g->eu, g->ev, E, hv, obj); }); }); });
+            case PF_ROWS: return launch(k_maxcut_obj_rows<T>, "k_maxcut_obj_rows", p, stream, xs, B, N, g->eu, g->ev, E, hv, obj);
+            default: return refuse(p);
         }
-    }
-    if (lds > (size_t)kLdsBytes && knob(KN_NARROW_TILE, 1) != 0)      // neither the 64-env nor the half tile fits: 16 or 8 envs per workgroup
-        if (const int rc = launch_obj_narrow(g, x, spin_bytes, B, obj, 0, stream); rc != kNarrowNo) return rc;
-    if (lds > (size_t)kLdsBytes) {   // neither tile fits: one env per wave on a byte row
-        const int rw = rows_waves(N);
-        RLS_REQUIRE(rw > 0, RLS_EUNSUPPORTED, "N=%lld: a row of %lld bytes does not fit LDS (max %d)", (long long)N, (long long)N, kLdsBytes);
-        const size_t lr = (size_t)rw * (((size_t)N + 15) & ~(size_t)15);
-        const dim3 gr((unsigned)ceil_div(B, rw)), br(rw * kWave);
-        const int hv = g->if_bidirectional ? 1 : 0;
-        if (spin_bytes == 1) {
-            if (lr > 64 * 1024) ensure_dyn_lds((const void*)k_maxcut_obj_rows<uint8_t>, lr);
-            hipLaunchKernelGGL(k_maxcut_obj_rows<uint8_t>, gr, br, lr, as_stream(stream), (const uint8_t*)x, B, N, g->eu, g->ev, E, hv, obj);
-        } else {
-            if (lr > 64 * 1024) ensure_dyn_lds((const void*)k_maxcut_obj_rows<float>, lr);
-            hipLaunchKernelGGL(k_maxcut_obj_rows<float>, gr, br, lr, as_stream(stream), (const float*)x, B, N, g->eu, g->ev, E, hv, obj);
-        }
-        return check_launch("k_maxcut_obj_rows");
-    }
-    const int P = pick_planes(E);
-    RLS_REQUIRE(P != 0, RLS_EUNSUPPORTED, "E'=%lld too large", (long long)E);
-    const bool vec = tile_rows_aligned(x, N, spin_bytes);
-    const int stage_off = tile_stage_offset(&lds, tw, spin_bytes == 1);   // (unaligned byte rows use it too)
-    const dim3 grid((unsigned)ceil_div(B, kWave)), block(tw * kWave);
-    hipStream_t s = as_stream(stream);
-    const int halve = g->if_bidirectional ? 1 : 0;
-    // dev knob: ask for more LDS than the tile needs, i.e. fewer resident workgroups per CU and a second round of them whose loads
-    // could hide the first round's counting (RLS_K1_LDS_KB = kilobytes per workgroup)
-    const int pad_kb = (int)knob(KN_K1_LDS_KB, 0);
-    if (pad_kb > 0 && (size_t)pad_kb * 1024 > lds && (size_t)pad_kb * 1024 <= (size_t)kLdsBytes) lds = (size_t)pad_kb * 1024;
-#define LAUNCH_OBJ(T, VEC, PP)                                                                             \
-    do {                                                                                                   \
-        auto kern = tw == kTileWavesMax ? k_maxcut_obj<T, VEC, PP, kTileWavesMax> : k_maxcut_obj<T, VEC, PP, kTileWaves>; \
-        if (lds > 64 * 1024)                                                                               \
-            ensure_dyn_lds((const void*)kern, lds); \
-        hipLaunchKernelGGL(kern, grid, block, lds, s, (const T*)x, B, N, g->eu, g->ev, E, halve, obj, stage_off); \
-    } while (0)
-#define DISPATCH_P(T, VEC)                       \
-    switch (P) {                                 \
-        case 12: LAUNCH_OBJ(T, VEC, 12); break;  \
-        case 16: LAUNCH_OBJ(T, VEC, 16); break;  \
-        case 20: LAUNCH_OBJ(T, VEC, 20); break;  \
-        default: LAUNCH_OBJ(T, VEC, 24); break;  \
-    }
-    if (spin_bytes == 1) {
-        if (vec) { DISPATCH_P(uint8_t, true) } else { DISPATCH_P(uint8_t, false) }
-    } else {
-        if (vec) { DISPATCH_P(float, true) } else { DISPATCH_P(float, false) }
-    }
-#undef DISPATCH_P
-#undef LAUNCH_OBJ
-    return check_launch("k_maxcut_obj");
+    };
+    return spin_bytes == 1 ? typed(uint8_t{}) : typed(float{});
 }
 
 int rls_maxcut_propose_accept(const rls_graph* g, uint8_t* x, int64_t B, const void* mask_v, int32_t mask_bits, int64_t* obj,
@@ -1947,100 +1593,25 @@ int rls_maxcut_propose_accept(const rls_graph* g, uint8_t* x, int64_t B, const v
     RLS_REQUIRE(x && mask && obj, RLS_EINVAL, "x/mask/obj is NULL");
     RLS_REQUIRE(!mask_bits || (((uintptr_t)mask) & 7) == 0, RLS_EINVAL, "a bit-packed mask is uint64 words: 8-byte aligned");
     const int64_t N = g->num_nodes, E = g->num_stored_edges;
-    if (const int nw = narrow_policy(N, B, tile_rows_aligned(x, N, 1) && (mask_bits || tile_rows_aligned(mask, N, 1)), KN_K6_TILE32))
-        if (const int rc = launch_propose_accept_narrow(g, x, B, mask, mask_bits, obj, nw, stream); rc != kNarrowNo) return rc;
-    int tw = tile_waves_for(N);
-    size_t lds = (size_t)N * 8 + (size_t)tw * kWave * 8;
-    if (lds > (size_t)kLdsBytes && (size_t)N * 8 + (size_t)kTileWaves * kWave * 8 <= (size_t)kLdsBytes) {
-        tw = kTileWaves;              // (as in rls_maxcut_obj: the tile alone fits, 4 waves without the row-piece stage)
-        lds = (size_t)N * 8 + (size_t)tw * kWave * 8;
+    const int hv = g->if_bidirectional ? 1 : 0;
+    const bool aligned = tile_rows_aligned(x, N, 1) && (mask_bits || tile_rows_aligned(mask, N, 1));
+    const LaunchPlan p = plan_propose_accept(shape_of(g, B, aligned, 1, mask_bits != 0));
+    switch (p.form) {
+        case PF_TILE64:
+            return with_bool(p.vec, [&](auto V) { return with_value<12, 16, 20, 24>(p.planes, [&](auto P) { return with_value<kTileWavesMax, kTileWaves>(p.waves, [&](auto W) {
+                return with_bool(mask_bits != 0, [&](auto MB) {
+                    return launch(k_maxcut_propose_accept<V(), P(), W(), MB()>, "k_maxcut_propose_accept", p, stream, x, mask, B, N, g->eu, g->ev, E, hv, obj, p.stage); }); }); }); });
+        case PF_TILE32:
+            return with_bool(p.vec, [&](auto V) { return with_value<12, 16, 20, 24>(p.planes, [&](auto P) { return with_value<kTileWavesMax, kTileWaves>(p.waves, [&](auto W) {
+                return with_bool(mask_bits != 0, [&](auto MB) {
+                    return launch(k_maxcut_propose_accept32<V(), P(), W(), MB()>, "k_maxcut_propose_accept32", p, stream, x, mask, B, N, g->eu, g->ev, E, hv, obj, p.stage); }); }); }); });
+        case PF_NARROW16: case PF_NARROW8:
+            return with_bool(p.vec, [&](auto V) { return with_value<16, 20, 24>(p.planes, [&](auto P) { return with_narrow_word(p, [&](auto w) {
+                return with_bool(mask_bits != 0, [&](auto MB) {
+                    return launch(k_maxcut_propose_accept_n<V(), P(), decltype(w), MB()>, "k_maxcut_propose_accept_n", p, stream, x, mask, B, N, g->eu, g->ev, E, hv, obj); }); }); }); });
+        case PF_ROWS: return launch(k_maxcut_propose_accept_rows, "k_maxcut_propose_accept_rows", p, stream, x, mask, B, N, g->eu, g->ev, E, hv, obj);
+        default: return refuse(p);
     }
-    // Half tiles (rls_tile32.h): where the 64-env tile does not fit and N * 4 bytes do, for rows past 8192 nodes (G70-sized 2^17,
-    // byte mask: 608 -> 481 us; N = 20 000 2^15, where the 64-env tile has no room for its stage: 387 -> 299), and in launches of
-    // at most one 64-env tile per CU (G22-sized 2^12: 21.8 -> 11.4 us, 2^14: 26.8 -> 20.9; at 2^16 they lose, 63.6 -> 67.3).
-    // tools/timing/k5_tile32.py.
-    const int knob32 = (int)knob(KN_K6_TILE32, -1);   // dev knob: 0 | 1 forces the choice
-    const bool no_stage64 = lds + (size_t)tw * kStageBytes > (size_t)kLdsBytes;
-    // (the half tile's fast loader wants byte rows of 16-byte multiples on a 16-byte base; other rows keep the 64-env forms)
-    const bool fast32 = (N & 7) == 0 && tile_rows_aligned(x, N, 1) && (mask_bits || tile_rows_aligned(mask, N, 1));
-    const bool want32 = knob32 >= 0 ? knob32 != 0
-                                    : fast32 && (no_stage64 || N >= 3000 || ceil_div(B, kWave) <= (int64_t)num_cus());
-    // (N >= 3000, round 5, as for K1: K6 with a byte mask at 2^16 envs, N = 3008 / 5008 / 7008: 101 / 173 / 236 -> 95 / 158 / 212 us,
-    // rows of 8-byte multiples 116 / 194 / 271 -> 101 / 165 / 236)
-    if (want32 || lds > (size_t)kLdsBytes) {
-        int w32 = kTileWavesMax;
-        auto lds32 = [&](int ww) { return (((size_t)N * 4 + 15) & ~(size_t)15) + (size_t)ww * kWave * 8; };
-        if (lds32(w32) > (size_t)kLdsBytes) w32 = kTileWaves;
-        size_t l32 = lds32(w32);
-        const int P32 = pick_planes(E);
-        if (l32 <= (size_t)kLdsBytes && P32 != 0) {
-            const bool vec = tile_rows_aligned(x, N, 1) && (mask_bits || tile_rows_aligned(mask, N, 1));
-            const int st32 = tile_stage_offset(&l32, w32, vec && (N & 7) == 0);    // (row-piece stages when they fit beside the tile)
-            const dim3 g32((unsigned)ceil_div(B, (int64_t)kHalf)), b32(w32 * kWave);
-            hipStream_t s32 = as_stream(stream);
-            const int hv = g->if_bidirectional ? 1 : 0;
-#define LAUNCH_PA32(VEC, PP)                                                                                            \
-    do {                                                                                                                \
-        auto kern = mask_bits ? (w32 == kTileWavesMax ? k_maxcut_propose_accept32<VEC, PP, kTileWavesMax, true>         \
-                                                      : k_maxcut_propose_accept32<VEC, PP, kTileWaves, true>)           \
-                              : (w32 == kTileWavesMax ? k_maxcut_propose_accept32<VEC, PP, kTileWavesMax, false>        \
-                                                      : k_maxcut_propose_accept32<VEC, PP, kTileWaves, false>);         \
-        if (l32 > 64 * 1024) ensure_dyn_lds((const void*)kern, l32); \
-        hipLaunchKernelGGL(kern, g32, b32, l32, s32, x, mask, B, N, g->eu, g->ev, E, hv, obj, st32);                    \
-    } while (0)
-#define DISPATCH_P32(VEC)                      \
-    switch (P32) {                             \
-        case 12: LAUNCH_PA32(VEC, 12); break;  \
-        case 16: LAUNCH_PA32(VEC, 16); break;  \
-        case 20: LAUNCH_PA32(VEC, 20); break;  \
-        default: LAUNCH_PA32(VEC, 24); break;  \
-    }
-            if (vec) { DISPATCH_P32(true) } else { DISPATCH_P32(false) }
-#undef DISPATCH_P32
-#undef LAUNCH_PA32
-            return check_launch("k_maxcut_propose_accept32");
-        }
-    }
-    if (lds > (size_t)kLdsBytes && knob(KN_NARROW_TILE, 1) != 0)      // neither the 64-env nor the half tile fits: 16 or 8 envs per workgroup
-        if (const int rc = launch_propose_accept_narrow(g, x, B, mask, mask_bits, obj, 0, stream); rc != kNarrowNo) return rc;
-    if (lds > (size_t)kLdsBytes) {   // neither tile fits: one env per wave on a byte row
-        const int rw = rows_waves(N);
-        RLS_REQUIRE(rw > 0, RLS_EUNSUPPORTED, "N=%lld: a row does not fit LDS (max %d)", (long long)N, kLdsBytes);
-        RLS_REQUIRE(!mask_bits, RLS_EUNSUPPORTED, "N=%lld: beyond the tiles the mask must be bytes [B, N]", (long long)N);
-        const size_t lr = (size_t)rw * (((size_t)N + 15) & ~(size_t)15);
-        if (lr > 64 * 1024) ensure_dyn_lds((const void*)k_maxcut_propose_accept_rows, lr);
-        hipLaunchKernelGGL(k_maxcut_propose_accept_rows, dim3((unsigned)ceil_div(B, rw)), dim3(rw * kWave), lr, as_stream(stream), x, mask, B, N,
-                           g->eu, g->ev, E, g->if_bidirectional ? 1 : 0, obj);
-        return check_launch("k_maxcut_propose_accept_rows");
-    }
-    const int P = pick_planes(E);
-    RLS_REQUIRE(P != 0, RLS_EUNSUPPORTED, "E'=%lld too large", (long long)E);
-    const bool vec = tile_rows_aligned(x, N, 1) && (mask_bits || tile_rows_aligned(mask, N, 1));
-    const int stage_off = tile_stage_offset(&lds, tw, true);
-    const dim3 grid((unsigned)ceil_div(B, kWave)), block(tw * kWave);
-    hipStream_t s = as_stream(stream);
-    const int halve = g->if_bidirectional ? 1 : 0;
-#define LAUNCH_PA(VEC, PP)                                                                                 \
-    do {                                                                                                   \
-        auto kern = mask_bits ? (tw == kTileWavesMax ? k_maxcut_propose_accept<VEC, PP, kTileWavesMax, true>   \
-                                                     : k_maxcut_propose_accept<VEC, PP, kTileWaves, true>)     \
-                              : (tw == kTileWavesMax ? k_maxcut_propose_accept<VEC, PP, kTileWavesMax>         \
-                                                     : k_maxcut_propose_accept<VEC, PP, kTileWaves>);          \
-        if (lds > 64 * 1024)                                                                               \
-            ensure_dyn_lds((const void*)kern, lds); \
-        hipLaunchKernelGGL(kern, grid, block, lds, s, x, mask, B, N, g->eu, g->ev, E, halve, obj, stage_off); \
-    } while (0)
-#define DISPATCH_P(VEC)                      \
-    switch (P) {                             \
-        case 12: LAUNCH_PA(VEC, 12); break;  \
-        case 16: LAUNCH_PA(VEC, 16); break;  \
-        case 20: LAUNCH_PA(VEC, 20); break;  \
-        default: LAUNCH_PA(VEC, 24); break;  \
-    }
-    if (vec) { DISPATCH_P(true) } else { DISPATCH_P(false) }
-#undef DISPATCH_P
-#undef LAUNCH_PA
-    return check_launch("k_maxcut_propose_accept");
 }
 
 int rls_maxcut_greedy_sweep(const rls_graph* g, uint8_t* x, int64_t B, int64_t* obj, void* stream) {
@@ -2048,181 +1619,37 @@ int rls_maxcut_greedy_sweep(const rls_graph* g, uint8_t* x, int64_t B, int64_t* 
     RLS_REQUIRE(B >= 0, RLS_EINVAL, "B < 0");
     if (B == 0) return RLS_OK;
     RLS_REQUIRE(x && obj, RLS_EINVAL, "x/obj is NULL");
-    const int64_t N = g->num_nodes;
-    const bool vec = tile_rows_aligned(x, N, 1);
-    if (const int nw = narrow_policy(N, B, vec, KN_K5_TILE32))
-        if (const int rc = launch_sweep_narrow(g, x, B, obj, nw, stream); rc != kNarrowNo) return rc;
-    const dim3 grid((unsigned)ceil_div(B, kWave)), block(kWave);
-    hipStream_t s = as_stream(stream);
-    const size_t lds_fast = (size_t)(N + 2) * 8 + (size_t)((N + 1 + 3) & ~3ll) * 4 + (size_t)kRing * 4;
-    const bool fast = !g->wgt && g->max_degree < kSweepMaxDeg && lds_fast <= (size_t)kLdsBytes &&
-                      (((uintptr_t)g->col) & 3) == 0;
-    {   // level-parallel sweep: needs the lane-per-node schedule (N < 2^20, degrees < 256) and the tile in LDS
-        const bool no_levels = knob_on(KN_SWEEP_NO_LEVELS);   // dev knob
-        const int64_t G = g->num_sweep_groups, E = g->num_stored_edges;
-        const int P = pick_planes(E);
-        const int force_lw = (int)knob(KN_SWEEP_WAVES, 0);
-        // one group per level (G22: 44 nodes per group): a level is ONE wave's pass and the others only prefetch -- few
-        // waves, more tiles per CU; well-filled groups (G70: 9 levels of ~17 groups): 8 waves share a level
-        int sw = force_lw == 2 || force_lw == 4 || force_lw == 8 || force_lw == 16 ? force_lw : (N >= 56 * G ? 8 : 4);
-        auto lds_of = [&](int waves, bool stage) {
-            return (size_t)(N + 2) * 8 + (((size_t)(G + 1) * 4 + 15) & ~(size_t)15) + (size_t)waves * kWave * 8 +
-                   (stage ? (size_t)kSweepLoadWaves * kStageBytes : 0);
-        };
-        int has_stage = 1;
-        if (lds_of(sw, true) > (size_t)kLdsBytes) {   // the tile nearly fills LDS (N ~ 20 000): no row-piece stage, fewer waves
-            has_stage = 0;
-            if (lds_of(sw, false) > (size_t)kLdsBytes) sw = 4;
-            if (lds_of(sw, false) > (size_t)kLdsBytes) sw = 2;
+    const int64_t N = g->num_nodes, E = g->num_stored_edges, G = g->num_sweep_groups;
+    const int hv = g->if_bidirectional ? 1 : 0;
+    const LaunchPlan p = plan_greedy_sweep(shape_of(g, B, tile_rows_aligned(x, N, 1)));
+    return with_bool(p.vec, [&](auto V) {
+        switch (p.form) {
+            case PF_TILE64:
+                return with_value<2, 4, 16, 8>(p.waves, [&](auto SW) { return with_value<12, 16, 20, 24>(p.planes, [&](auto P) {
+                    return launch(k_maxcut_greedy_sweep_levels<V(), SW(), P()>, "k_maxcut_greedy_sweep_levels", p, stream, x, B, N, g->sweep_lv_ptr, g->sweep_lv_data, G,
+                                  g->eu, g->ev, E, hv, obj, p.stage); }); });
+            case PF_TILE32:      // (no 16-wave form)
+                return with_value<2, 4, 8>(p.waves, [&](auto SW) { return with_value<12, 16, 20, 24>(p.planes, [&](auto P) {
+                    return launch(k_maxcut_greedy_sweep_levels32<V(), SW(), P()>, "k_maxcut_greedy_sweep_levels32", p, stream, x, B, N, g->sweep_lv_ptr, g->sweep_lv_data, G,
+                                  g->eu, g->ev, E, hv, obj, p.stage); }); });
+            case PF_NARROW16: case PF_NARROW8:
+                return with_value<16, 20, 24>(p.planes, [&](auto P) { return with_narrow_word(p, [&](auto w) {
+                    return launch(k_maxcut_greedy_sweep_levels_n<V(), P(), decltype(w)>, "k_maxcut_greedy_sweep_levels_n", p, stream, x, B, N, g->sweep_lv_ptr,
+                                  g->sweep_lv_data, G, g->eu, g->ev, E, hv, obj); }); });
+            case PF_SWEEP_BATCHED:
+                return with_value<16, 8, 4>(p.waves, [&](auto SW) {
+                    return launch(k_maxcut_greedy_sweep_batched<V(), SW()>, "k_maxcut_greedy_sweep_batched", p, stream, x, B, N, g->sweep_rowptr, g->sweep_stream,
+                                  g->nnz + N, obj); });
+            case PF_SWEEP_FAST: return launch(k_maxcut_greedy_sweep<V()>, "k_maxcut_greedy_sweep", p, stream, x, B, N, g->rowptr, g->col, g->nnz, obj);
+            case PF_ROWS:      // the symmetric CSR counts every undirected edge once per endpoint: the gain of a flip needs no halving
+                return with_bool(g->wgt != nullptr, [&](auto W) {
+                    return launch(k_maxcut_greedy_sweep_rows<W()>, "k_maxcut_greedy_sweep_rows", p, stream, x, B, N, g->rowptr, g->col, g->wgt, 0, obj); });
+            case PF_SWEEP_GENERIC:
+                return with_bool(g->wgt != nullptr, [&](auto W) {
+                    return launch(k_maxcut_greedy_sweep_generic<V(), W()>, "k_maxcut_greedy_sweep_generic", p, stream, x, B, N, g->rowptr, g->col, g->wgt, obj); });
+            default: return refuse(p);
         }
-        const size_t lds_l = lds_of(sw, has_stage != 0);
-        // half tiles (rls_tile32.h) where the 64-env tile does not fit (dev knob RLS_K5_TILE32 = 1: at any size)
-        const int knob32 = (int)knob(KN_K5_TILE32, -1);
-        // ... and, for byte rows of 16-byte multiples (the half tile's staged loader / store), where they measure faster
-        // (tools/timing/k5_tile32.py): rows past 8192 nodes (G70-sized 2^17: 780 -> 705 us; N = 20 000, where the 64-env tile has no
-        // room for its stage, 4096 envs: 171 -> 100) and launches of at most one 64-env tile per CU (G22-sized 2^14: 63 -> 53 us;
-        // at 2^16 the half tiles lose, 113 -> 128: twice the schedule reads per env)
-        const bool prefer32 = knob32 < 0 && vec && (N & 7) == 0 &&
-                              (!has_stage || (size_t)N * 8 > 64 * 1024 || ceil_div(B, kWave) <= (int64_t)num_cus());
-        if ((knob32 > 0 || prefer32 || lds_l > (size_t)kLdsBytes) && !no_levels && !g->wgt && g->sweep_lv_ptr && g->sweep_lv_data && G > 0 && P != 0) {
-            int sw32 = force_lw == 2 || force_lw == 4 || force_lw == 8 ? force_lw : (N >= 56 * G ? 8 : 4);
-            auto lds32_of = [&](int waves, bool stage) {
-                return (((size_t)(N + 2) * 4 + 15) & ~(size_t)15) + (((size_t)(G + 1) * 4 + 15) & ~(size_t)15) + (size_t)waves * kWave * 8 +
-                       (stage ? (size_t)kSweepLoadWaves * kStageBytes : 0);
-            };
-            int stage32 = vec && (N & 7) == 0 ? 1 : 0;
-            if (stage32 && lds32_of(sw32, true) > (size_t)kLdsBytes) stage32 = 0;
-            if (lds32_of(sw32, stage32 != 0) > (size_t)kLdsBytes) sw32 = 4;
-            if (lds32_of(sw32, stage32 != 0) > (size_t)kLdsBytes) sw32 = 2;
-            // a half tile that leaves room for two waves only (N ~ 40 000: the words fill LDS) sweeps slower than 16-env tiles with
-            // eight at every batch size (N = 39 936: 2^12 envs 356 -> 135 us, 2^16 3779 -> 2332)
-            if (sw32 == 2 && knob(KN_NARROW_TILE, 1) == 1 && knob32 < 0)
-                if (const int rc = launch_sweep_narrow(g, x, B, obj, 16, stream); rc != kNarrowNo) return rc;
-            const size_t l32 = lds32_of(sw32, stage32 != 0);
-            if (l32 <= (size_t)kLdsBytes) {
-                const dim3 g32((unsigned)ceil_div(B, (int64_t)kHalf)), b32(sw32 * kWave);
-                const int hv = g->if_bidirectional ? 1 : 0;
-#define LAUNCH_SWL32(VEC, SWV, PP)                                                                                          \
-    do {                                                                                                                    \
-        auto kern = k_maxcut_greedy_sweep_levels32<VEC, SWV, PP>;                                                           \
-        if (l32 > 64 * 1024) ensure_dyn_lds((const void*)kern, l32); \
-        hipLaunchKernelGGL(kern, g32, b32, l32, s, x, B, N, g->sweep_lv_ptr, g->sweep_lv_data, G, g->eu, g->ev, E, hv, obj, stage32); \
-    } while (0)
-#define DISPATCH_SWL32_P(VEC, SWV)                       \
-    switch (P) {                                         \
-        case 12: LAUNCH_SWL32(VEC, SWV, 12); break;      \
-        case 16: LAUNCH_SWL32(VEC, SWV, 16); break;      \
-        case 20: LAUNCH_SWL32(VEC, SWV, 20); break;      \
-        default: LAUNCH_SWL32(VEC, SWV, 24); break;      \
-    }
-#define DISPATCH_SWL32(VEC)                                     \
-    do {                                                        \
-        if (sw32 == 4) { DISPATCH_SWL32_P(VEC, 4) }             \
-        else if (sw32 == 2) { DISPATCH_SWL32_P(VEC, 2) }        \
-        else { DISPATCH_SWL32_P(VEC, 8) }                       \
-    } while (0)
-                if (vec) DISPATCH_SWL32(true); else DISPATCH_SWL32(false);
-#undef DISPATCH_SWL32
-#undef DISPATCH_SWL32_P
-#undef LAUNCH_SWL32
-                return check_launch("k_maxcut_greedy_sweep_levels32");
-            }
-            // the half tile does not fit either: 16 or 8 envs per workgroup (the same level schedule)
-            if (knob(KN_NARROW_TILE, 1) != 0)
-                if (const int rc = launch_sweep_narrow(g, x, B, obj, 0, stream); rc != kNarrowNo) return rc;
-        }
-        if (!no_levels && !g->wgt && g->sweep_lv_ptr && g->sweep_lv_data && G > 0 && P != 0 && lds_l <= (size_t)kLdsBytes) {
-            const dim3 blockl(sw * kWave);
-            const int halve = g->if_bidirectional ? 1 : 0;
-#define LAUNCH_SWL(VEC, SWV, PP)                                                                             \
-    do {                                                                                                     \
-        auto kern = k_maxcut_greedy_sweep_levels<VEC, SWV, PP>;                                              \
-        if (lds_l > 64 * 1024)                                                                               \
-            ensure_dyn_lds((const void*)kern, lds_l); \
-        hipLaunchKernelGGL(kern, grid, blockl, lds_l, s, x, B, N, g->sweep_lv_ptr, g->sweep_lv_data, G, g->eu, g->ev, \
-                           E, halve, obj, has_stage);                                                         \
-    } while (0)
-#define DISPATCH_SWL_P(VEC, SWV)                       \
-    switch (P) {                                       \
-        case 12: LAUNCH_SWL(VEC, SWV, 12); break;      \
-        case 16: LAUNCH_SWL(VEC, SWV, 16); break;      \
-        case 20: LAUNCH_SWL(VEC, SWV, 20); break;      \
-        default: LAUNCH_SWL(VEC, SWV, 24); break;      \
-    }
-#define DISPATCH_SWL(VEC)                                       \
-    do {                                                        \
-        if (sw == 16) { DISPATCH_SWL_P(VEC, 16) }               \
-        else if (sw == 4) { DISPATCH_SWL_P(VEC, 4) }            \
-        else if (sw == 2) { DISPATCH_SWL_P(VEC, 2) }            \
-        else { DISPATCH_SWL_P(VEC, 8) }                         \
-    } while (0)
-            if (vec) DISPATCH_SWL(true); else DISPATCH_SWL(false);
-#undef DISPATCH_SWL
-#undef DISPATCH_SWL_P
-#undef LAUNCH_SWL
-            return check_launch("k_maxcut_greedy_sweep_levels");
-        }
-    }
-    const bool unbatched = knob_on(KN_SWEEP_UNBATCHED);   // dev knob
-    if (fast && g->sweep_rowptr && g->sweep_stream && !unbatched) {
-        const int force_sw = (int)knob(KN_SWEEP_WAVES, 0);   // dev knob
-        const int sw = force_sw == 4 || force_sw == 8 || force_sw == 16 ? force_sw
-                                                                         : (ceil_div(B, kWave) <= (int64_t)num_cus() ? 16 : 8);
-        const size_t lds_b = lds_fast + (size_t)sw * kWave * 8;
-        const dim3 blockw(sw * kWave);
-#define LAUNCH_SWB(VEC)                                                                                    \
-    do {                                                                                                   \
-        auto kern = sw == 16 ? k_maxcut_greedy_sweep_batched<VEC, 16>                                      \
-                             : (sw == 8 ? k_maxcut_greedy_sweep_batched<VEC, 8> : k_maxcut_greedy_sweep_batched<VEC, 4>); \
-        if (lds_b > 64 * 1024)                                                                             \
-            ensure_dyn_lds((const void*)kern, lds_b); \
-        hipLaunchKernelGGL(kern, grid, blockw, lds_b, s, x, B, N, g->sweep_rowptr, g->sweep_stream, g->nnz + N, obj); \
-    } while (0)
-        if (lds_b <= (size_t)kLdsBytes) {
-            if (vec) LAUNCH_SWB(true); else LAUNCH_SWB(false);
-            return check_launch("k_maxcut_greedy_sweep_batched");
-        }
-#undef LAUNCH_SWB
-    }
-    if (fast) {
-#define LAUNCH_SWF(VEC)                                                                                    \
-    do {                                                                                                   \
-        auto kern = k_maxcut_greedy_sweep<VEC>;                                                            \
-        if (lds_fast > 64 * 1024)                                                                          \
-            ensure_dyn_lds((const void*)kern, lds_fast); \
-        hipLaunchKernelGGL(kern, grid, block, lds_fast, s, x, B, N, g->rowptr, g->col, g->nnz, obj);       \
-    } while (0)
-        if (vec) LAUNCH_SWF(true); else LAUNCH_SWF(false);
-#undef LAUNCH_SWF
-        return check_launch("k_maxcut_greedy_sweep");
-    }
-    const size_t lds = (size_t)N * 8;
-    if (lds > (size_t)kLdsBytes) {   // the 64-env bit tile does not fit: one env per wave on a byte row
-        const int rw = rows_waves(N);
-        RLS_REQUIRE(rw > 0, RLS_EUNSUPPORTED, "N=%lld: a row does not fit LDS (max %d)", (long long)N, kLdsBytes);
-        const size_t lr = (size_t)rw * (((size_t)N + 15) & ~(size_t)15);
-        const dim3 gr((unsigned)ceil_div(B, rw)), br(rw * kWave);
-        // the symmetric CSR counts every undirected edge once per endpoint: the gain of a flip needs no halving
-        if (g->wgt) {
-            if (lr > 64 * 1024) ensure_dyn_lds((const void*)k_maxcut_greedy_sweep_rows<true>, lr);
-            hipLaunchKernelGGL(k_maxcut_greedy_sweep_rows<true>, gr, br, lr, s, x, B, N, g->rowptr, g->col, g->wgt, 0, obj);
-        } else {
-            if (lr > 64 * 1024) ensure_dyn_lds((const void*)k_maxcut_greedy_sweep_rows<false>, lr);
-            hipLaunchKernelGGL(k_maxcut_greedy_sweep_rows<false>, gr, br, lr, s, x, B, N, g->rowptr, g->col, g->wgt, 0, obj);
-        }
-        return check_launch("k_maxcut_greedy_sweep_rows");
-    }
-#define LAUNCH_SW(VEC, W)                                                                                  \
-    do {                                                                                                   \
-        auto kern = k_maxcut_greedy_sweep_generic<VEC, W>;                                                 \
-        if (lds > 64 * 1024)                                                                               \
-            ensure_dyn_lds((const void*)kern, lds); \
-        hipLaunchKernelGGL(kern, grid, block, lds, s, x, B, N, g->rowptr, g->col, g->wgt, obj);            \
-    } while (0)
-    if (g->wgt) { if (vec) LAUNCH_SW(true, true); else LAUNCH_SW(false, true); }
-    else        { if (vec) LAUNCH_SW(true, false); else LAUNCH_SW(false, false); }
-#undef LAUNCH_SW
-    return check_launch("k_maxcut_greedy_sweep_generic");
+    });
 }
 
 int rls_maxcut_edge_cut_mask(const rls_graph* g, const uint8_t* x, int64_t B, uint8_t* cutmask, void* stream) {
@@ -2236,24 +1663,57 @@ int rls_maxcut_edge_cut_mask(const rls_graph* g, const uint8_t* x, int64_t B, ui
     return check_launch("k_edge_cut_mask");
 }
 
-static inline size_t node_stats_lds(int64_t N) { return (size_t)(N + 2) * 8 + (size_t)kTileWaves * kWave * 144; }
-// the lane = env tile kernels (weighted graphs, degrees >= 65536) walk every node and entry of the graph once per tile, 0.10 us
-// per node + 0.008 us per entry whatever the batch (K3 on a +-1-weighted G22-sized graph: 530 us from 2048 to 16 384 envs), the
-// element-parallel kernels 2.75e-6 us per (env, node + entry) (250 / 480 / 1890 us at 2048 / 4096 / 16 384): the tile form from
-// the batch where it is the cheaper one (tools/sweeps/node_stats_forms.py)
-static inline bool node_stats_use_tile(const rls_graph* g, int64_t B) {
-    const bool off = knob_on(KN_NODE_STATS_NO_TILE);   // dev knob
-    const int64_t N = g->num_nodes;
-    return !off && node_stats_lds(N) <= (size_t)kLdsBytes &&
-           2.75e-6 * (double)B * (double)(N + g->nnz) > 0.103 * (double)N + 0.008 * (double)g->nnz;
+}  // extern "C" (a template follows)
+
+// K2 / K3 / the local-search weights on the bit-sliced tiles (MODE 0 / 1 / 2).  `rowptr`, `ell_ptr`, `ell`: the adjacency the entry reads
+template <int MODE, typename WT = int32_t>
+static int launch_node_stats_bits(const LaunchPlan& p, const rls_graph* g, const uint8_t* x, int64_t B, const int32_t* rowptr,
+                                  const int32_t* ell_ptr, const int32_t* ell, int mult, void* out, void* stream,
+                                  int32_t* minmax = nullptr, int64_t out_pitch = 0) {
+    const int64_t N = g->num_nodes, pitch = out_pitch > 0 ? out_pitch : N;
+    return with_bool(p.vec, [&](auto V) {
+        switch (p.form) {
+            case PF_TILE64:
+                if (p.waves == 4)      // (RLS_NS_WAVES = 4: degrees below 256 only)
+                    return launch(k_node_stats_bits<MODE, V(), false, WT, 4>, "k_node_stats_bits", p, stream, x, B, N, rowptr, ell_ptr, ell, mult, out, minmax, pitch, p.stage);
+                return with_bool(p.wide, [&](auto WIDE) {
+                    return launch(k_node_stats_bits<MODE, V(), WIDE(), WT>, "k_node_stats_bits", p, stream, x, B, N, rowptr, ell_ptr, ell, mult, out, minmax, pitch, p.stage); });
+            case PF_TILE32:
+                return with_bool(p.wide, [&](auto WIDE) {
+                    return launch(k_node_stats_bits32<MODE, V(), WIDE(), WT>, "k_node_stats_bits32", p, stream, x, B, N, rowptr, ell_ptr, ell, mult, out, minmax, pitch, p.stage); });
+            default:      // PF_NARROW16 / PF_NARROW8
+                return with_bool(p.wide, [&](auto WIDE) { return with_narrow_word(p, [&](auto w) {
+                    return launch(k_node_stats_bits32<MODE, V(), WIDE(), WT, decltype(w)>, "k_node_stats_bits32<narrow>", p, stream, x, B, N, rowptr, ell_ptr, ell, mult, out, minmax,
+                                  pitch, p.stage); }); });
+        }
+    });
 }
 
+extern "C" {
+
 // which kernel family K2 / K3 / the local-search weights take for a batch of B envs: 1 bit-sliced (lane = node), 2 lane = env
-// tile, 0 element-parallel -- the launchers' own tests (what = 0: K2 / weights, the adjacency as stored; 1: K3, symmetric)
+// tile, 0 element-parallel -- the launchers' own plan (what = 0: K2 / weights, the adjacency as stored; 1: K3, symmetric)
 int rls_maxcut_node_stats_form(const rls_graph* g, int64_t B, int32_t what) {
-    if (!g || g->num_nodes <= 0 || B <= 0) return 0;
-    if (what ? node_stats_use_bits(g, g->ell_sym_ptr, g->ell_sym, B) : node_stats_use_bits(g, g->ell_st_ptr, g->ell_st, B)) return 1;
-    return node_stats_use_tile(g, B) ? 2 : 0;
+    rls_launch_plan p;
+    if (!g || g->num_nodes <= 0 || B <= 0 || rls_maxcut_launch_plan(g, what ? RLS_PLAN_K3 : RLS_PLAN_K2, B, 0, 256, &p) != RLS_OK) return 0;
+    return p.form == PF_NS_ELEM ? 0 : p.form == PF_NS_TILE ? 2 : 1;      // (the family does not depend on the CU count)
+}
+
+// the plan an entry point would launch (include/rlsolver_hip.h): the launchers' own planner on a shape given by values
+int rls_maxcut_launch_plan(const rls_graph* g, int32_t what, int64_t B, int32_t flags, int32_t cus, rls_launch_plan* out) {
+    RLS_REQUIRE(g && g->num_nodes > 0 && out && B > 0 && what >= RLS_PLAN_K1 && what <= RLS_PLAN_WEIGHTS, RLS_EINVAL, "bad arguments");
+    const int elt = flags & RLS_PLAN_F32 ? 4 : 1;
+    const void* base = reinterpret_cast<const void*>((uintptr_t)(flags & RLS_PLAN_BASE_UNALIGNED ? 4 : 16));      // (an address of that alignment)
+    TileShape s = shape_of(g, B, tile_rows_aligned(base, g->num_nodes, elt), elt, (flags & RLS_PLAN_MASK_BITS) != 0,
+                           what == RLS_PLAN_K3 ? g->ell_sym_ptr && g->ell_sym : g->ell_st_ptr && g->ell_st,
+                           flags & RLS_PLAN_OUT_UNALIGNED ? base : nullptr, what == RLS_PLAN_WEIGHTS && !(flags & RLS_PLAN_NO_MINMAX) ? base : nullptr, cus);
+    if (flags & RLS_PLAN_OUT_UNALIGNED) s.out16 = false;
+    const LaunchPlan p = what == RLS_PLAN_K1   ? plan_obj(s)
+                         : what == RLS_PLAN_K6 ? plan_propose_accept(s)
+                         : what == RLS_PLAN_K5 ? plan_greedy_sweep(s)
+                                               : plan_node_stats(s, what - RLS_PLAN_K2);
+    *out = rls_launch_plan{p.form, p.waves, p.planes, p.vec, p.wide, p.stage, p.grid, p.block, (int64_t)p.lds, p.err};
+    return RLS_OK;
 }
 
 int rls_maxcut_node_cutdeg(const rls_graph* g, const uint8_t* x, int64_t B, int64_t* cutdeg, void* stream) {
@@ -2261,27 +1721,15 @@ int rls_maxcut_node_cutdeg(const rls_graph* g, const uint8_t* x, int64_t B, int6
     RLS_REQUIRE(B >= 0, RLS_EINVAL, "B < 0");
     if (B == 0) return RLS_OK;
     RLS_REQUIRE(x && cutdeg, RLS_EINVAL, "x/cutdeg is NULL");
-    if (node_stats_use_bits(g, g->ell_st_ptr, g->ell_st, B))
-        return launch_node_stats_bits<0>(g, x, B, g->erowptr, g->ell_st_ptr, g->ell_st, 0, cutdeg, stream);
     const int64_t N = g->num_nodes;
-    const size_t lds = node_stats_lds(N);
-    if (node_stats_use_tile(g, B)) {
-        const dim3 grid((unsigned)ceil_div(B, kWave)), block(kTileWaves * kWave);
-        hipStream_t s = as_stream(stream);
-#define LAUNCH_NS(VEC)                                                                                           \
-    do {                                                                                                         \
-        auto kern = k_node_stats_tile<int64_t, false, false, VEC>;                                               \
-        if (lds > 64 * 1024)                                                                                     \
-            ensure_dyn_lds((const void*)kern, lds);  \
-        hipLaunchKernelGGL(kern, grid, block, lds, s, x, B, N, g->erowptr, g->ev, (const int32_t*)nullptr, cutdeg); \
-    } while (0)
-        if (tile_rows_aligned(x, N, 1)) LAUNCH_NS(true); else LAUNCH_NS(false);
-#undef LAUNCH_NS
-        return check_launch("k_node_stats_tile<cutdeg>");
+    const LaunchPlan p = plan_node_stats(shape_of(g, B, tile_rows_aligned(x, N, 1), 1, false, g->ell_st_ptr && g->ell_st, cutdeg), 0);
+    switch (p.form) {
+        case PF_NS_TILE:
+            return with_bool(p.vec, [&](auto V) {
+                return launch(k_node_stats_tile<int64_t, false, false, V()>, "k_node_stats_tile<cutdeg>", p, stream, x, B, N, g->erowptr, g->ev, nullptr, cutdeg); });
+        case PF_NS_ELEM: return launch(k_node_cutdeg, "k_node_cutdeg", p, stream, x, B, N, g->erowptr, g->ev, cutdeg);
+        default: return launch_node_stats_bits<0>(p, g, x, B, g->erowptr, g->ell_st_ptr, g->ell_st, 0, cutdeg, stream);
     }
-    hipLaunchKernelGGL(k_node_cutdeg, dim3(grid_for(B * N, 256)), dim3(256), 0, as_stream(stream), x, B, N, g->erowptr,
-                       g->ev, cutdeg);
-    return check_launch("k_node_cutdeg");
 }
 
 int rls_maxcut_delta_all(const rls_graph* g, const uint8_t* x, int64_t B, int32_t* delta, void* stream) {
@@ -2289,34 +1737,16 @@ int rls_maxcut_delta_all(const rls_graph* g, const uint8_t* x, int64_t B, int32_
     RLS_REQUIRE(B >= 0, RLS_EINVAL, "B < 0");
     if (B == 0) return RLS_OK;
     RLS_REQUIRE(x && delta, RLS_EINVAL, "x/delta is NULL");
-    if (node_stats_use_bits(g, g->ell_sym_ptr, g->ell_sym, B))
-        return launch_node_stats_bits<1>(g, x, B, g->rowptr, g->ell_sym_ptr, g->ell_sym, 0, delta, stream);
     const int64_t N = g->num_nodes;
-    const size_t lds = node_stats_lds(N);
-    if (node_stats_use_tile(g, B)) {
-        const dim3 grid((unsigned)ceil_div(B, kWave)), block(kTileWaves * kWave);
-        hipStream_t s = as_stream(stream);
-#define LAUNCH_ND(W, VEC)                                                                                        \
-    do {                                                                                                         \
-        auto kern = k_node_stats_tile<int32_t, true, W, VEC>;                                                    \
-        if (lds > 64 * 1024)                                                                                     \
-            ensure_dyn_lds((const void*)kern, lds);  \
-        hipLaunchKernelGGL(kern, grid, block, lds, s, x, B, N, g->rowptr, g->col, g->wgt, delta);               \
-    } while (0)
-        const bool vec = tile_rows_aligned(x, N, 1);
-        if (g->wgt) { if (vec) LAUNCH_ND(true, true); else LAUNCH_ND(true, false); }
-        else        { if (vec) LAUNCH_ND(false, true); else LAUNCH_ND(false, false); }
-#undef LAUNCH_ND
-        return check_launch("k_node_stats_tile<delta>");
+    const LaunchPlan p = plan_node_stats(shape_of(g, B, tile_rows_aligned(x, N, 1), 1, false, g->ell_sym_ptr && g->ell_sym, delta), 1);
+    switch (p.form) {
+        case PF_NS_TILE:
+            return with_bool(g->wgt != nullptr, [&](auto W) { return with_bool(p.vec, [&](auto V) {
+                return launch(k_node_stats_tile<int32_t, true, W(), V()>, "k_node_stats_tile<delta>", p, stream, x, B, N, g->rowptr, g->col, g->wgt, delta); }); });
+        case PF_NS_ELEM:
+            return with_bool(g->wgt != nullptr, [&](auto W) { return launch(k_delta_all<W()>, "k_delta_all", p, stream, x, B, N, g->rowptr, g->col, g->wgt, delta); });
+        default: return launch_node_stats_bits<1>(p, g, x, B, g->rowptr, g->ell_sym_ptr, g->ell_sym, 0, delta, stream);
     }
-    const dim3 grid(grid_for(B * N, 256)), block(256);
-    if (g->wgt)
-        hipLaunchKernelGGL(k_delta_all<true>, grid, block, 0, as_stream(stream), x, B, N, g->rowptr, g->col, g->wgt,
-                           delta);
-    else
-        hipLaunchKernelGGL(k_delta_all<false>, grid, block, 0, as_stream(stream), x, B, N, g->rowptr, g->col, g->wgt,
-                           delta);
-    return check_launch("k_delta_all");
 }
 
 }  // extern "C" (a template follows)
@@ -2324,13 +1754,9 @@ int rls_maxcut_delta_all(const rls_graph* g, const uint8_t* x, int64_t B, int32_
 template <typename WT>
 static int ls_weights_typed(const rls_graph* g, const uint8_t* x, int64_t B, int32_t mult, WT* ws, int64_t pitch, int32_t* minmax,
                             void* stream) {
-    // (a lane = env tile kernel used to take the small batches: 850 us per call on a G22-sized graph at any batch size, against
-    // 30 us for the bit-sliced one and 20 - 100 us for the element-parallel one: tools/sweeps/ls_weights_forms.py)
-    if (node_stats_use_bits(g, g->ell_st_ptr, g->ell_st, B))
-        return launch_node_stats_bits<2, WT>(g, x, B, g->erowptr, g->ell_st_ptr, g->ell_st, (int)mult, ws, stream, minmax, pitch);
-    hipLaunchKernelGGL(k_ls_weights_elem<WT>, dim3(grid_for(B * g->num_nodes, 256)), dim3(256), 0, as_stream(stream), x, B, g->num_nodes,
-                       g->erowptr, g->ev, (int)mult, ws, pitch, minmax);
-    return check_launch("k_ls_weights_elem");
+    const LaunchPlan p = plan_node_stats(shape_of(g, B, tile_rows_aligned(x, g->num_nodes, 1), 1, false, g->ell_st_ptr && g->ell_st, ws, minmax), 2);
+    if (p.form != PF_NS_ELEM) return launch_node_stats_bits<2, WT>(p, g, x, B, g->erowptr, g->ell_st_ptr, g->ell_st, (int)mult, ws, stream, minmax, pitch);
+    return launch(k_ls_weights_elem<WT>, "k_ls_weights_elem", p, stream, x, B, g->num_nodes, g->erowptr, g->ev, (int)mult, ws, pitch, minmax);
 }
 
 extern "C" {

@@ -4,7 +4,7 @@
 // EXACTLY-sized heap buffers, built with -fsanitize=address,undefined by tests/test_sanitize.py.  Every builder runs
 // its sizing call first and then fills buffers of exactly that size, so a one-past-the-end write is an ASAN report;
 // structural invariants (every node scheduled once, levels respect the dependency order, ELL rows complete) are checked
-// on top.  Exit code 0 = clean.  CPU only: sanitizers do not run on the GPU box.
+// on top.  The MaxCut launch planner (csrc/rls_maxcut_plan.h, host-only C++) runs over random shapes beside them.  Exit code 0 = clean.  CPU only: sanitizers do not run on the GPU box.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "rlsolver_hip.h"
+#include "rls_maxcut_plan.h"      // the MaxCut launch planner: host-only C++, so it runs under the sanitizers too
 
 #include "../oracle/oracle.h"
 
@@ -249,6 +250,23 @@ static void run_oracle(const Graph& g, std::mt19937_64& rng) {
     orc_tsp_tour_length(dist.p, T, perm.p, B, len.p);
 }
 
+// every planner over random shapes (sizes up to past every LDS limit, every flag, random knobs): no overflow, no plan past the LDS
+static void run_planners(std::mt19937_64& rng) {
+    rls::TileShape s{};
+    s.N = 1 + (int64_t)(rng() % 200000); s.B = 1 + (int64_t)(rng() % (1 << 17)); s.E = (int64_t)(rng() % (1 << 25));
+    s.nnz = 2 * s.E; s.G = (int64_t)(rng() % (s.N / 32 + 2)); s.spin_bytes = rng() & 1 ? 1 : 4; s.max_degree = (int32_t)(rng() % 70000);
+    const uint64_t f = rng();
+    s.rows_aligned = f & 1; s.out16 = f & 2; s.mask_bits = f & 4; s.minmax = f & 8; s.weighted = (f & 48) == 48;
+    s.has_levels = f & 64; s.has_batches = f & 128; s.has_ell = f & 256; s.col4 = f & 512; s.cus = 1 + (int)(rng() % 512);
+    if (f & 1024) rls_tuning_set(f & 2048 ? "RLS_NARROW_TILE" : "RLS_NS_TILE32", (int64_t)(rng() % 4));
+    const rls::LaunchPlan plans[] = {rls::plan_obj(s), rls::plan_propose_accept(s), rls::plan_greedy_sweep(s), rls::plan_node_stats(s, 0),
+                                     rls::plan_node_stats(s, 1), rls::plan_node_stats(s, 2)};
+    for (const rls::LaunchPlan& p : plans)
+        CHECK(p.form == rls::PF_UNSUPPORTED ? p.err == RLS_EUNSUPPORTED && p.msg[0] != 0 : p.lds <= (size_t)rls::kLdsBytes && p.grid >= 1 && p.block >= 64,
+              "plan form %d lds %zu grid %u block %u", p.form, p.lds, p.grid, p.block);
+    rls_tuning_unset(nullptr);
+}
+
 int main(int argc, char** argv) {
     const int iters = argc > 1 ? std::atoi(argv[1]) : 200;
     std::mt19937_64 rng(argc > 2 ? (uint64_t)std::atoll(argv[2]) : 20261003ull);
@@ -262,6 +280,7 @@ int main(int argc, char** argv) {
         Graph g = make_graph(rng, kind);
         run_builders(g, rng);
         run_oracle(g, rng);
+        for (int k = 0; k < 50; ++k) run_planners(rng);
     }
     std::printf("host_sanitize: %d random graphs through the host builders and the C oracle, clean\n", iters);
     return 0;
