@@ -6,11 +6,15 @@
 //          gain = deg - 2c); weighted graphs a wave shuffle reduction.
 //   emit : the run is streamed with 16-byte vectors, the flipped spin patched in flight.
 //
-// Three emit structures (which one runs where: see the launcher):
+// Emit structures (which one runs where: see the launcher):
 //   MODE 0  gain first (gathers from global), then copy           -- first version
 //   MODE 1  issue the copy's loads first, compute the gain while they fly, patch, store
 //   MODE 2  stage the run in LDS with direct global->LDS loads (no VGPR round trip), gather
 //           the neighbours from LDS, patch the byte in LDS, stream LDS -> HBM
+//   MODE 3  MODE 2's staging with the stores chasing the loads, the flip applied in registers
+// MODE 2 on 1-byte rows with write-through stores (the headline's form) requests obj, the CSR
+// row bounds and the neighbour ids beside the run, so that the LDS stage is held for one memory
+// latency, not for a chain of them; the other staged forms keep the order of round 7.
 #include "rls_tile.h"
 #include <cstdlib>
 
@@ -121,6 +125,20 @@ __global__ __launch_bounds__(256) void k_maxcut_step(const T* __restrict__ xin, 
     }
 
     int my_delta = 0;  // lane k keeps env k's gain
+    // publish with obj_old = lane k's obj[b0 + k] as it stood before this step, requested before the run (MODE 2, headline form)
+    auto publish_from = [&](int obj_old) {
+        if (lane < nenv) {
+            const int64_t b = b0 + lane;
+            bool ok = false;
+#pragma unroll
+            for (int k = 0; k < EPW; ++k) if (lane == k) ok = act[k] >= 0;
+            const int v = obj_old + my_delta;
+            obj[b] = v;
+            reward[b] = ok ? (float)my_delta : __builtin_nanf("");
+            if (cur) cur[b] = (float)v;
+            if (done) done[b] = done_value;
+        }
+    };
     auto publish = [&]() {
         if (lane < nenv) {
             const int64_t b = b0 + lane;
@@ -250,6 +268,136 @@ __global__ __launch_bounds__(256) void k_maxcut_step(const T* __restrict__ xin, 
                 }
             }
             tail_copy();
+        } else if constexpr (MODE == 2 && ST == kStWt && sizeof(T) == 1) {
+            // MODE 2, 1-byte rows, write-through stores (the headline's form; the other staged forms follow below, in the order of
+            // round 7: the new order has been measured on this form only).  LDS staged.  Per-wave region of EPW*N*sizeof(T) bytes (16-byte multiple) + 128.
+            // A run starts 16-byte aligned, not 128-byte aligned (rows of 2000 or 10 000 bytes: a run starts 0, 16, ... 112 bytes
+            // into a cache line), and a 1 KB wave-instruction that starts mid-line touches NINE lines instead of eight -- the
+            // texture path prices lines: rows of 12 000 / 15 984 / 16 016 bytes ran at 0.63 of HBM, rows of 12 288 / 16 000 /
+            // 16 128 at 0.71 - 0.73.  So the instruction boundaries are put on the lines of the GLOBAL side: vector i of the run
+            // lives in LDS slot i + h (h = 16-byte units between the line's start and the run's, 0..7; the region has 128
+            // spare bytes), the first load instruction carries 64 - h vectors, every later one starts on a line; the stores likewise
+            // with the output's own h.
+            //
+            // The wave's LDS stage is what limits a CU to 16 waves, so nothing but the run's own latency may hold it: every operand
+            // of the gain is requested BESIDE the run, none after it (round 8; before, the run was waited for first, then EPW
+            // serial rowptr -> col round trips, then the gather, then obj's load inside publish).  Order of a trip:
+            //   1  obj[b0 + lane]                      needs nothing; the oldest op on the vector-memory counter
+            //   2  the run's LDS-DMA
+            //   3  all EPW rowptr pairs                scalar loads from a clamped index: unconditional, ONE wait for the lot
+            //   4  all EPW col loads (+ wgt)           only for a node that has neighbours
+            //   5  a short last run's element tail     inside a wave-uniform branch: the common path has no join with loads of
+            //                                          its own, at which the compiler would drain the counter before 3
+            //   6  one wait, the gather
+            //   7  publish from the preloaded obj
+            // The vector loads of 1 and 4 are hand-issued and hand-waited: beside a pending LDS-DMA the compiler waits vmcnt(0)
+            // for any load it tracks -- at its use, and already at the head of a loop it is pending at.
+            // INVARIANT of a hand-issued load: between the asm that issues it and the hand-written wait the compiler must neither
+            // copy nor spill its destination register (obj_old, nb[], wv[]) -- it believes the value is there already, and a copy
+            // taken early would be garbage, silently.  Nothing enforces this;
+            // it is checked by reading the ISA of the instantiations (no scratch, no v_mov / v_accvgpr of those registers before
+            // the wait) whenever this block or its register pressure changes.
+            unsigned char* region = smem + (size_t)wib * ((size_t)EPW * N * sizeof(T) + kStepPad);
+            const int h_src = (int)((reinterpret_cast<uintptr_t>(src) >> 4) & 7), h_dst = (int)((reinterpret_cast<uintptr_t>(dst) >> 4) & 7);
+            const int h_in = align_lines ? h_src : 0, h_out = align_lines ? h_dst : 0;
+            V* region_v = reinterpret_cast<V*>(region);
+            V* stage_v = region_v + h_in;
+            T* stage = reinterpret_cast<T*>(stage_v);
+            int obj_old;
+            {   // (lanes past the run's envs read env b0's: in bounds, never used)
+                const int32_t* po = obj + b0 + (lane < nenv ? lane : 0);
+                asm volatile("global_load_dword %0, %1, off" : "=v"(obj_old) : "v"(po) : "memory");
+            }
+            for (int64_t slot0 = 0; slot0 < nvec + h_in; slot0 += kWave) {
+                const int64_t i = slot0 + lane - h_in;
+                if (i >= 0 && i < nvec) glds16<NTL>(src + i, region_v + slot0);  // LDS dst = wave base + lane*16
+            }
+            int r0[EPW], deg[EPW], nb[EPW], wv[EPW];
+#pragma unroll
+            for (int k = 0; k < EPW; ++k) {
+                // an invalid action reads node 0's bounds, which nothing below uses (no select on the loaded words: the compiler
+                // turns one into a branch round the second load, with a wait of its own per env)
+                const int64_t ai = act[k] < 0 ? 0 : act[k];
+                r0[k] = rowptr[ai];
+                deg[k] = rowptr[ai + 1];
+            }
+            __builtin_amdgcn_sched_barrier(0);   // (or the scheduler lifts the first subtraction, and its wait, between the loads)
+#pragma unroll
+            for (int k = 0; k < EPW; ++k) deg[k] -= r0[k];
+#pragma unroll
+            for (int k = 0; k < EPW; ++k) {
+                nb[k] = 0; wv[k] = 0;
+                // Only for a node that HAS neighbours (deg is wave-uniform: a scalar branch): an isolated node at the end of
+                // the CSR has r0 == nnz, and col + nnz is one entry past the array (col may be NULL when nnz == 0).  Lanes past
+                // the row's end read its first entry.
+                if (act[k] >= 0 && deg[k] > 0) {
+                    const int32_t* pn = col + r0[k] + (lane < deg[k] ? lane : 0);
+                    asm volatile("global_load_dword %0, %1, off" : "=v"(nb[k]) : "v"(pn) : "memory");
+                    if constexpr (WEIGHTED) {
+                        const int32_t* pw = wgt + r0[k] + (lane < deg[k] ? lane : 0);
+                        asm volatile("global_load_dword %0, %1, off" : "=v"(wv[k]) : "v"(pw) : "memory");
+                    }
+                }
+            }
+            if (nvec * PER < nel) {   // a short last run: its elements past the last whole vector are staged by hand (the gain reads them)
+                for (int64_t i = nvec * PER + lane; i < nel; i += kWave) stage[i] = xin[b0 * N + i];
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+            // the compiler does not know that the hand-issued loads only become valid at a hand-written wait: every use goes through
+            // a value it must treat as (re)defined HERE, after that wait
+            auto operands_landed = [&]() {
+                asm volatile("" : "+v"(obj_old) :: "memory");
+#pragma unroll
+                for (int k = 0; k < EPW; ++k) {
+                    asm volatile("" : "+v"(nb[k]) :: "memory");
+                    if constexpr (WEIGHTED) asm volatile("" : "+v"(wv[k]) :: "memory");
+                }
+            };
+            // gains from the staged (unpatched) rows
+            auto gather = [&]() {
+#pragma unroll
+                for (int k = 0; k < EPW; ++k)
+                    if (act[k] >= 0) {
+                        const T* row = stage + (int64_t)k * N;
+                        const bool xa = spin_is_set(row[act[k]]);
+                        int d;
+                        if (deg[k] <= kWave) {
+                            const bool on = lane < deg[k];
+                            const bool xn = on ? spin_is_set(row[nb[k]]) : xa;
+                            if constexpr (WEIGHTED) d = wave_sum_i32(on ? ((xn == xa) ? wv[k] : -wv[k]) : 0);
+                            else d = deg[k] - 2 * __popcll(ballot64(xn != xa));
+                        } else {
+                            d = flip_gain<T, WEIGHTED>(row, act[k], rowptr, col, wgt, lane);
+                        }
+                        if (lane == k) my_delta = d;
+                    }
+            };
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_wave_barrier();
+            operands_landed();
+            gather();
+            publish_from(obj_old);
+            __builtin_amdgcn_wave_barrier();
+            if (lane < nenv) {
+                int64_t a = -1;
+#pragma unroll
+                for (int k = 0; k < EPW; ++k) if (lane == k) a = act[k];
+                if (a >= 0) {
+                    T* p = stage + (int64_t)lane * N + a;
+                    *p = spin_flip<T>(*p);
+                }
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll 4
+            for (int64_t slot0 = 0; slot0 < nvec + h_out; slot0 += kWave) {
+                const int64_t i = slot0 + lane - h_out;
+                if (i >= 0 && i < nvec) st_vec<ST>(dst + i, stage_v[i]);
+            }
+            for (int64_t i = nvec * PER + lane; i < nel; i += kWave) xout[b0 * N + i] = stage[i];
+            // a persistent wave's next trip refills this stage by LDS-DMA: none of its ds_reads may still be outstanding
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_wave_barrier();
         } else if constexpr (MODE == 3) {
             // MODE 3: MODE 2's staging with the stores CHASING the loads.  The flip needs no gain (a gym step flips its action node
             // whatever the reward), so 1 KB piece j of the run can leave as soon as it has landed: the wave's stores are in flight
@@ -305,7 +453,9 @@ __global__ __launch_bounds__(256) void k_maxcut_step(const T* __restrict__ xin, 
                 }
             }
             tail_copy();                                                     // (a short last run only)
-            wait_vmcnt_le(nch < 62 ? nch : 62);                              // the neighbour ids are older than every store
+            // the neighbour ids are older than every store, and at least nch store instructions are younger than them: EVERY trip j of
+            // the loop above issues one (with h <= 7 each of the nch pieces holds a vector of the run: no trip has an empty lane mask)
+            wait_vmcnt_le(nch < 62 ? nch : 62);
             // the compiler does not know that nb[k] only became valid at the wait above: every use below goes through a value it
             // must treat as (re)defined HERE, after the wait
 #pragma unroll
@@ -479,6 +629,11 @@ extern "C" int rls_maxcut_step(const rls_graph* g, const void* x_in, void* x_out
     const int64_t nch_run = ceil_div((int64_t)run_bytes, 16 * kWave);
     // measured (tools/sweep_step.py, SW_CHASE=0,1): f32 rows gain 3 - 6 % (N = 10^4: 0.674 -> 0.701; N = 2000: 0.707 -> 0.752 of
     // 8 TB/s), 1-byte rows nothing (0.694 / 0.694, 0.738 / 0.739): their runs are 8 - 10 pieces, back before the first could leave
+    // (the f32 figures are round 6 / 7's; MODE 3 and MODE 2 on f32 rows are the code they were taken on.)  Round 8, after MODE 2 on 1-byte
+    // rows with write-through stores got its operands beside the run (profiles/r08_sweep.txt): G22 u8 write-through 39.9 us, chase +
+    // write-through 42.9, plain 44.8, nontemporal 47.2 with or without chase -- no chase, write-through; G70 u8 2^17 nontemporal
+    // 466.9 us, write-through 469.9, plain 488.1 -- nontemporal above the Infinity Cache.  Open: nontemporal + chase takes 439.8 us at
+    // G70 u8, 5.8 % under this rule's pick; one measured point, not yet a rule (DESIGN_HISTORY section 12)
     const bool chase = staged && nch_run + 1 + epw <= 62 && (knobs.chase > 0 || (knobs.chase < 0 && spin_bytes == 4));   // (+ 1: a shifted run's extra piece)
     const bool nts = knobs.nts >= 0 ? knobs.nts != 0 : ((size_t)B * N * spin_bytes > ((size_t)256 << 20));
     // write-through in place of plain stores: MODE 2 by default (measured: tools/ceilings/ring_copy.hip, bench.py); MODE 3 when forced
