@@ -786,6 +786,22 @@ int rls_isco_maxcut_step(const rls_graph* g, const float* x, float* y_out, int64
                          int64_t env_offset, float* energy_out, float* acc_out, float* terms_out, uint8_t* mask_out,
                          void* scratch, int64_t scratch_bytes, void* stream);
 
+/* ISCO_MIS.step(x, path_length, temperature)  envs/env_ISCO.py:111-174 in ONE kernel: rls_isco_maxcut_step with the energy of
+ * the maximum-independent-set sampler (model :162-170) in place of the cut,
+ *   ll_x = (sum_i x_i - lam * pairs(x)) / T,  pairs = edge-list entries (u, v) with x_u = x_v = 1: a duplicated line counts
+ *          twice, a loop (u, u) once when u is set;
+ *   log_prob = log_softmax((1 - 2 x_i) (1 - lam * cnt_i) / 2T),  cnt_i = set neighbours of i over its row entries (a loop is
+ *          listed twice in its row)  -- the closed form of get_local_dist's autograd (:134-146).
+ * Everything else is rls_isco_maxcut_step's contract, word for word: x / y_out / path_length (clamped to [1, N]) / the two
+ * draws (both given or both NULL: the same generator and key layout, (seed, env_offset + b, node)) / the outputs and the
+ * terms_out layout / y_out must not alias x / RLS_EUNSUPPORTED past the byte rows' limit.  lam (the reference's LAMADA = 1.001)
+ * must be finite.  g as ISCO_maxcut builds it: one row entry per end of every edge-list line, loops kept.
+ * scratch: rls_isco_maxcut_scratch_bytes(g, B) -- the rows and their layout are the same. */
+int rls_isco_mis_step(const rls_graph* g, const float* x, float* y_out, int64_t B, const int64_t* path_length,
+                      float temperature, float lam, const float* u_gumbel, const float* u_accept, uint64_t seed,
+                      int64_t env_offset, float* energy_out, float* acc_out, float* terms_out, uint8_t* mask_out,
+                      void* scratch, int64_t scratch_bytes, void* stream);
+
 /* ISCO_TSP.step(x, path_length, temperature)  envs/env_ISCO.py:188-236 in ONE kernel (one wave per env, the tour,
  * its inverse and -- when it fits -- the distance matrix in LDS): path_length times { opt_2 (:238-335: partner
  * city per position from the nearest / random tables, swap delta, ban mask) -> logits = -delta / 2T (banned:

@@ -116,4 +116,7 @@ def __getattr__(name):
     if name == "ISCO_maxcut":
         from .env_ISCO_maxcut import ISCO_maxcut
         return ISCO_maxcut
+    if name == "ISCO_MIS":          # env_ISCO.py:93-174
+        from .env_ISCO_MIS import ISCO_MIS
+        return ISCO_MIS
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

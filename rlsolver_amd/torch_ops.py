@@ -55,7 +55,7 @@ DEVICE_ENTRY_POINTS = [
     "best_update", "best_key", "key_unpack", "winner_message", "winner_unpack", "rand_spins", "rand_spins_repeats", "rand_actions", "rand_perms", "spin_reset", "spin_step", "spin_observation", "spin_materialize", "spin_reset_dense", "spin_step_dense", "rand_couplings", "mcpg_metro_rounds", "mcpg_metro_stop", "mcpg_local_search",
     "mcpg_local_search_levels", "mcpg_pick_best", "mcpg_merge_best", "mcpg_value_bit_sums", "mcpg_pack_chains", "mcpg_unpack_chains",
     "qubo_local_search_value", "qubo_sparse_local_search_value", "tsp_tour_length", "tsp_swap_delta_all", "tsp_apply_swap", "tsp_2opt_delta", "tsp_2opt_best", "isco_maxcut_step",
-    "isco_tsp_step",
+    "isco_mis_step", "isco_tsp_step",
 ]
 # declared in the header but not device work: host-side schedule builders and queries (plain C calls, no op)
 HOST_ENTRY_POINTS = [

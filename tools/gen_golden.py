@@ -1472,6 +1472,90 @@ def gen_isco_steps():
     save("isco_steps", **out)
 
 
+def gen_isco_mis():
+    """ISCO_MIS (envs/env_ISCO.py:93-174): get_local_dist at two temperatures and three full steps with every torch draw
+    recorded, on two graphs of the data directory and on one small edge list read by the reference's own
+    ISCO/util_maxcut.load_data from a file that repeats and reverses lines -- the loader keeps num_edges entries and networkx
+    merges those lines, so the arrays end in (0, 0) entries: loops on node 0, where the MIS energy and the cut part ways."""
+    import tempfile
+    import rlsolver.envs.env_ISCO as env_isco
+    from rlsolver.methods.ISCO import util_maxcut
+    from rlsolver.methods.util_read_data import read_mygraph
+    B = 12
+    env_isco.BATCH_SIZE = B
+    env_isco.DEVICE = util_maxcut.DEVICE = th.device("cpu")
+    out = {"lam": np.float32(env_isco.LAMADA)}
+    cases = []
+    for gname in ("BA_100_ID0", "PL_20_ID0"):
+        g = graph_arrays(read_mygraph(os.path.join(DATA, GRAPHS[gname])))
+        n = int(g[:, :2].max()) + 1
+        cases.append((gname, n, th.from_numpy(g[:, 0].copy()), th.from_numpy(g[:, 1].copy())))
+    lines = [(1, 2), (2, 3), (3, 4), (4, 5), (5, 4), (4, 5), (2, 1), (6, 7), (7, 8), (8, 6), (6, 8), (9, 10), (10, 11), (11, 12),
+             (12, 13), (13, 1), (1, 13), (3, 9), (9, 3), (5, 11), (2, 7), (7, 2), (7, 2), (1, 6)]
+    with tempfile.NamedTemporaryFile("w", suffix=".txt", delete=False) as f:
+        f.write(f"13 {len(lines)}\n" + "".join(f"{a} {b} 1\n" for a, b in lines))
+    try:
+        data = util_maxcut.load_data(f.name)
+    finally:
+        os.unlink(f.name)
+    assert data["num_edges"] == len(lines) and int((data["edge_from"] == data["edge_to"]).sum()) >= 5      # the (0, 0) padding
+    cases.append(("loader_13", data["num_nodes"], data["edge_from"].clone(), data["edge_to"].clone()))
+    for gname, n, eu, ev in cases:
+        params = {"num_nodes": n, "num_edges": len(eu), "edge_from": eu, "edge_to": ev}
+        smp = env_isco.ISCO_MIS(params)
+        out[f"{gname}/graph"] = np.stack([eu.numpy(), ev.numpy(), np.ones(len(eu), np.int64)], axis=1).astype(np.int64)
+        th.manual_seed(5)
+        x = smp.random_gen_init_sample(params)
+        out[f"{gname}/x"] = u8(x)
+        out[f"{gname}/x_dtype"] = np.array(str(x.dtype))
+        for T in (1.0, 0.37):
+            energy, logp = smp.get_local_dist(x, th.tensor(T))
+            out[f"{gname}/T{T}/energy"] = energy.numpy().copy()
+            out[f"{gname}/T{T}/log_prob"] = logp.numpy().copy()
+        cap = {}
+        o_prop, o_y2x, o_sel = smp.proposal, smp.ll_y2x, smp.select_sample
+
+        def w_prop(x, pl, T):
+            r = o_prop(x, pl, T)
+            cap["ll_x"], cap["y_prop"] = r[0].clone(), r[1].clone()
+            cap["ll_x2y"], cap["mask"] = r[2]["ll_x2y"].clone(), r[2]["selected_idx"]["selected_mask"].clone()
+            return r
+
+        def w_y2x(tr, y, T):
+            r = o_y2x(tr, y, T)
+            cap["ll_y"], cap["ll_y2x"] = r[0].clone(), r[1].clone()
+            return r
+
+        def w_sel(la, x, y):
+            cap["log_acc"] = la.clone()
+            return o_sel(la, x, y)
+
+        smp.proposal, smp.ll_y2x, smp.select_sample = w_prop, w_y2x, w_sel
+        gen = th.Generator().manual_seed(15)
+        for k, T in enumerate((1.0, 0.5, 0.2)):
+            pl = th.randint(1, min(n, 14), (B,), generator=gen)
+            pl[0], pl[1] = 1, n                      # the two ends of the clamp in main_ISCO_MIS.py:26
+            th.manual_seed(100 + k)
+            with Recorder("rand") as rec:
+                y, energy, acc = smp.step(x, pl, th.tensor(T))
+            assert len(rec.log["rand"]) == 2
+            tag = f"{gname}/step{k}"
+            out[f"{tag}/x"] = u8(x)
+            out[f"{tag}/path_length"] = pl.numpy().copy()
+            out[f"{tag}/temperature"] = np.float32(T)
+            out[f"{tag}/rand_gumbel"] = rec.log["rand"][0].numpy().copy()
+            out[f"{tag}/rand_accept"] = rec.log["rand"][1].numpy().copy()
+            for kk in ("ll_x", "ll_x2y", "ll_y", "ll_y2x", "log_acc"):
+                out[f"{tag}/{kk}"] = cap[kk].numpy().copy()
+            out[f"{tag}/mask"] = u8(cap["mask"])
+            out[f"{tag}/y_prop"] = u8(cap["y_prop"])
+            out[f"{tag}/y"] = u8(y)
+            out[f"{tag}/energy"] = energy.numpy().copy()
+            out[f"{tag}/acc"] = acc.numpy().copy()
+            x = y
+    save("isco_mis", **out)
+
+
 API_FILES = (
     "rlsolver/envs/env_L2A.py", "rlsolver/envs/env_MCPG.py", "rlsolver/envs/env_PPO.py", "rlsolver/envs/env_ISCO.py",
     "rlsolver/methods/LocalSearch.py", "rlsolver/methods/MCPG.py", "rlsolver/methods/util_evaluator.py",
@@ -1608,7 +1692,7 @@ def gen_graph_forms():
     save("maxcut_graph_forms", **out)
 
 
-ALL = {"graph_forms": gen_graph_forms, "mcpg_weighted": gen_mcpg_weighted, "isco_steps": gen_isco_steps, "spinsystem_cpu": gen_spinsystem_cpu, "spinsystem": gen_spinsystem, "spinsystem_perenv": gen_spinsystem_perenv, "qubo": gen_qubo, "qubo_asym": gen_qubo_asym, "isco_maxcut": gen_isco_maxcut, "maxcut": gen_maxcut, "sweep": gen_sweep, "lsclass": gen_local_search_class, "ppo": gen_ppo,
+ALL = {"graph_forms": gen_graph_forms, "mcpg_weighted": gen_mcpg_weighted, "isco_steps": gen_isco_steps, "isco_mis": gen_isco_mis, "spinsystem_cpu": gen_spinsystem_cpu, "spinsystem": gen_spinsystem, "spinsystem_perenv": gen_spinsystem_perenv, "qubo": gen_qubo, "qubo_asym": gen_qubo_asym, "isco_maxcut": gen_isco_maxcut, "maxcut": gen_maxcut, "sweep": gen_sweep, "lsclass": gen_local_search_class, "ppo": gen_ppo,
        "select": gen_select, "mcpg": gen_mcpg, "tsp": gen_tsp, "tsp_2opt": gen_tsp_2opt, "encoder": gen_encoder,
        "wgain": gen_weighted_gain, "mcpg_glue": gen_mcpg_glue, "evaluator": gen_evaluator, "spinsystem_options": gen_spinsystem_options,
        "api_surface": gen_api_surface, "mcpg_data": gen_mcpg_data,
