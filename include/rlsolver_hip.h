@@ -723,7 +723,8 @@ int rls_tsp_tour_length(const float* dist, int64_t N, const int64_t* perm, int64
  *   selected == NULL (production): the partners are drawn IN the kernel from (seed, env_offset + b, i) -- the generator and the
  *     counters of rls_isco_tsp_step's iteration 0 -- through nearest int32 [N, K] / random int32 [N, random_stride]
  *     (random_stride >= N - K - 1; or their byte form tables8, below), near_threshold = K / (K + 1); selected_out (may be
- *     NULL) records them, int64 [B,N].
+ *     NULL) records them, int64 [B,N].  1 <= K <= N - 2 (RLS_EINVAL otherwise): the far draw needs a non-empty table, as the
+ *     reference's randint(0, N - K - 1) does.
  *     Algorithmic bytes per tour: 8N in, 13N out.
  *   selected != NULL (the recorded-draw hook of the golden tests): int64 [B,N] partner cities, tables / seed ignored. */
 int rls_tsp_swap_delta_all(const float* dist, int64_t N, const int64_t* perm, int64_t B, const int64_t* selected,
@@ -732,8 +733,31 @@ int rls_tsp_swap_delta_all(const float* dist, int64_t N, const int64_t* perm, in
                            float* logratio, int64_t* indices, uint8_t* ban, void* stream);
 /* tables8 (may be NULL; N <= 256): the same two tables as BYTES for the kernel to keep in LDS beside the distance matrix --
  * rls_tsp_tables8_bytes(N, K) bytes, 4-byte aligned: uint8 [N, K] nearest, zero-padded to a multiple of 16 bytes, then uint8
- * [N, N - K - 1] = the first N - K - 1 columns of random, zero-padded likewise (0 = no byte form for this N / K). */
+ * [N, N - K - 1] = the first N - K - 1 columns of random, zero-padded likewise (0 = no byte form for this N / K: N > 256, or K outside [1, N - 2]). */
 int64_t rls_tsp_tables8_bytes(int64_t N, int32_t K);
+
+/* [host] The form a TSP entry point takes at these sizes: the launchers' own arithmetic (csrc/rls_tsp_plan.h -- they call the
+ * same functions), nothing is launched and no device is needed; what tests assert the form they mean to reach with.
+ *   what = RLS_TSP_TOUR_LENGTH (K12), RLS_TSP_SWAP_DELTA (K13: K and has_tables8 describe the in-kernel draw -- has_tables8 = 1:
+ *   selected == NULL and the caller passes tables8; 0: tables8 == NULL or recorded `selected`, K ignored), RLS_TSP_STEP
+ *   (rls_isco_tsp_step), RLS_TSP_2OPT_BEST / _EXACT (cur_length == NULL / given), RLS_TSP_RAND_PERMS.  K and has_tables8 are
+ *   read for RLS_TSP_SWAP_DELTA only.
+ * Fills *out; returns RLS_EINVAL for N < 1, an unknown `what` or out == NULL.  A size the entry point refuses is NOT an error
+ * here: supported = 0 (the entry point returns RLS_EUNSUPPORTED before any launch), the other fields 0.
+ * Additive (the ABI stays v12). */
+enum { RLS_TSP_TOUR_LENGTH = 0, RLS_TSP_SWAP_DELTA = 1, RLS_TSP_STEP = 2, RLS_TSP_2OPT_BEST = 3, RLS_TSP_RAND_PERMS = 4,
+       RLS_TSP_2OPT_BEST_EXACT = 5 };
+enum { RLS_TSP_KERNEL_ONLY = 0, RLS_TSP_KERNEL_PERMS_LDS = 1, RLS_TSP_KERNEL_PERMS_GLOBAL = 2 };
+typedef struct rls_tsp_form {
+    int32_t lds_d;      /* 1: the distance matrix is staged in LDS (the LDS_D = true instantiation) */
+    int32_t tab8;       /* 1: K13 keeps the byte tables in LDS (TAB8 = true; implies lds_d) */
+    int32_t block;      /* threads per workgroup */
+    int32_t waves;      /* waves per workgroup (K12 / K13 / the step: tours in flight per workgroup) */
+    int64_t lds_bytes;  /* dynamic LDS bytes of the launch */
+    int32_t kernel;     /* RLS_TSP_KERNEL_*: which of rls_rand_perms' two kernels; RLS_TSP_KERNEL_ONLY elsewhere */
+    int32_t supported;  /* 0: the entry point returns RLS_EUNSUPPORTED at this size */
+} rls_tsp_form;
+int rls_tsp_launch_form(int32_t what, int64_t N, int32_t K, int32_t has_tables8, rls_tsp_form* out);
 
 /* ISCO_TSP.switch  envs/env_ISCO.py:337-344 for one chosen position per env:
  * if pos[b] >= 0 swap perm[b, (pos[b]+1) % N] and perm[b, indices[b, pos[b]]]. */

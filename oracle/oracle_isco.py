@@ -12,9 +12,23 @@ its torch draws recorded): see tests/test_oracle_isco.py.  Only tests/ may impor
 """
 from __future__ import annotations
 
+import contextlib
+
 import numpy as np
 
 F = np.float32
+
+
+@contextlib.contextmanager
+def precision(dtype):
+    """Run the restatement in another float type (np.float64: the reference-against-reference gap of the tolerance tools).
+    Inputs keep the type the caller gives them: pass float64 matrices and draws for a float64 run."""
+    global F
+    old, F = F, dtype
+    try:
+        yield
+    finally:
+        F = old
 
 
 def log_softmax(x):
@@ -145,9 +159,13 @@ def tsp_opt_2(sample, dist, nearest, random, K, temperature, u_partner, r_near, 
 
 
 def tsp_step(x, dist, nearest, random, K, path_length, temperature, u_partner, r_near, r_rand, u_gumbel, u_accept):
-    """ISCO_TSP.step, env_ISCO.py:188-201 -> dict(log_acc, cur_x, y, mean_acc)"""
+    """ISCO_TSP.step, env_ISCO.py:188-201 -> dict(log_acc, cur_x, y, mean_acc) and, for the tests' gating only: argmax_margin
+    [L, B] = the lead of each round's selected position over the runner-up (perturbed log-probabilities), argmax_scale [L, B]
+    = the larger |log-probability| of the two, selected [L, B] = the position each round took, banned [L, B] = whether it was banned."""
     B, N = x.shape
     cur = x.copy()
+    margin, scale = np.zeros((path_length, B)), np.zeros((path_length, B))
+    selected, banned = np.zeros((path_length, B), np.int64), np.zeros((path_length, B), bool)
     traj = np.zeros((B, 3, path_length), F)
     one = np.ones(B, np.int64)
     for i in range(path_length):
@@ -157,6 +175,11 @@ def tsp_step(x, dist, nearest, random, K, path_length, temperature, u_partner, r
         log_prob = log_softmax(logits)
         mask, perturbed, ll_sel = multinomial(log_prob, one, u_gumbel[i])
         logits2 = (logits * (1 - 2 * mask)).astype(F)
+        top = np.argsort(-perturbed, axis=-1, kind="stable")[:, :2]
+        two = np.take_along_axis(perturbed, top, axis=-1).astype(np.float64)
+        margin[i] = two[:, 0] - two[:, 1]
+        scale[i] = np.abs(np.take_along_axis(log_prob, top, axis=-1)).max(axis=-1)
+        selected[i], banned[i] = top[:, 0], ban[np.arange(B), top[:, 0]]
         env, posn = np.nonzero((mask == 1) & ~ban)
         nxt = cur.copy()
         j = indices[env, posn]
@@ -171,4 +194,5 @@ def tsp_step(x, dist, nearest, random, K, path_length, temperature, u_partner, r
     log_acc = np.minimum(traj.sum(axis=(1, 2), dtype=F), F(0)).astype(F)
     use = mh_accept(log_acc, u_accept)
     y = np.where(use[:, None], cur, x)
-    return dict(log_acc=log_acc, cur_x=cur, y=y, mean_acc=np.exp(log_acc).astype(F).mean(dtype=F))
+    return dict(log_acc=log_acc, cur_x=cur, y=y, mean_acc=np.exp(log_acc).astype(F).mean(dtype=F), argmax_margin=margin,
+                argmax_scale=scale, selected=selected, banned=banned)

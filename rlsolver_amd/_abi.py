@@ -68,6 +68,16 @@ class RlsSpinEnv(C.Structure):
 
 _SE = C.POINTER(RlsSpinEnv)
 
+
+class RlsTspForm(C.Structure):
+    """struct rls_tsp_form: what rls_tsp_launch_form answers (host query, no device)."""
+    _fields_ = [("lds_d", C.c_int32), ("tab8", C.c_int32), ("block", C.c_int32), ("waves", C.c_int32), ("lds_bytes", C.c_int64),
+                ("kernel", C.c_int32), ("supported", C.c_int32)]
+
+
+TSP_TOUR_LENGTH, TSP_SWAP_DELTA, TSP_STEP, TSP_2OPT_BEST, TSP_RAND_PERMS, TSP_2OPT_BEST_EXACT = range(6)
+TSP_KERNEL_ONLY, TSP_KERNEL_PERMS_LDS, TSP_KERNEL_PERMS_GLOBAL = range(3)
+
 # name -> argtypes; every function returns int.  Keep in sync with include/rlsolver_hip.h
 # (tests/test_abi.py parses the header and checks this table against it).
 SIGNATURES = {
@@ -131,6 +141,7 @@ SIGNATURES = {
     "rls_winner_message": [_P, _I64, _I64, _P, _P, C.c_int32, _I64, _I64, _P, _P],
     "rls_winner_unpack": [_P, _I64, _P, _P, _P],
     "rls_maxcut_launch_plan": [_G, C.c_int32, _I64, C.c_int32, C.c_int32, _P],
+    "rls_tsp_launch_form": [C.c_int32, _I64, C.c_int32, C.c_int32, _P],
     "rls_tuning_set": [_P, _I64],
     "rls_tuning_unset": [_P],
     "rls_tuning_get": [_P, _P, _P],
@@ -192,6 +203,13 @@ def version() -> int:
 
 def device_count() -> int:
     return lib().rls_device_count()
+
+
+def tsp_launch_form(what: int, N: int, K: int = 0, has_tables8: bool = False) -> RlsTspForm:
+    """The form a TSP entry point takes at these sizes (rls_tsp_launch_form: the launchers' own arithmetic, nothing is launched)."""
+    f = RlsTspForm()
+    call("rls_tsp_launch_form", int(what), int(N), int(K), int(bool(has_tables8)), C.byref(f))
+    return f
 
 
 # ---- tuning table (ABI v11): explicit, in-process; the production library reads no environment variable ----

@@ -18,6 +18,7 @@
 // the tolerance north_star states for floating-point results).
 #include "rls_tile.h"
 #include "rls_draw.h"
+#include "rls_tsp_plan.h"
 #include <cmath>
 #include <cstdlib>
 
@@ -925,15 +926,11 @@ int rls_isco_tsp_step(const float* dist, int64_t N, const int32_t* nearest, int3
     RLS_REQUIRE(!test || (u_partner && r_near && r_rand && u_gumbel && u_accept), RLS_EINVAL,
                 "test draws must be given all together");
     RLS_REQUIRE(temperature > 0.0f, RLS_EINVAL, "temperature must be > 0");
-    const size_t per_wave = (size_t)N * 16;
-    const size_t dbytes = (size_t)N * N * 4;
-    const bool lds_d = dbytes + 4 * per_wave <= (size_t)kLdsBytes - 1024;
-    int waves = 4;
-    if (!lds_d) {
-        RLS_REQUIRE(per_wave <= (size_t)kLdsBytes, RLS_EUNSUPPORTED, "N=%lld too large for the per-env tour scratch", (long long)N);
-        while (waves > 1 && per_wave * waves > (size_t)kLdsBytes) waves >>= 1;
-    }
-    const size_t lds = (lds_d ? dbytes : 0) + per_wave * waves;
+    const TspForm f = tsp_plan_step(N);
+    RLS_REQUIRE(f.err == RLS_OK, f.err, "N=%lld too large for the per-env tour scratch", (long long)N);
+    const bool lds_d = f.lds_d;
+    const int waves = f.waves;
+    const size_t lds = f.lds;
     IscoTspArgs a{dist, N, K, random_stride, near_threshold, nearest, random, perm_in, perm_out, B, path_length, temperature, u_partner, r_near, r_rand,
                   u_gumbel, u_accept, seed, env_offset, log_acc_out, acc_out, cur_out};
     const dim3 grid((unsigned)ceil_div(B, waves)), block(waves * kWave);

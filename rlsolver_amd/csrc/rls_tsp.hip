@@ -7,11 +7,11 @@
 #include "rls_tile.h"
 #include "rls_ring.h"
 #include "rls_draw.h"
+#include "rls_tsp_plan.h"
 
 namespace rls {
 
-constexpr int kTspBlock = 1024;     // launch bound; small tours use it whole (32 waves/CU hide the HBM round trip)
-constexpr int kTspBlockSmall = 256;  // large N: the per-wave LDS tour scratch limits waves per workgroup
+// (kTspBlock, kTspBlockSmall, kPermStride and the choice of form: rls_tsp_plan.h)
 
 __device__ __forceinline__ float wave_sum_f32(float v) {
 #pragma unroll
@@ -233,7 +233,6 @@ __global__ void k_rand_perms(int64_t* __restrict__ perm, int64_t B, int64_t N, u
 // halfwords = 33 dwords, so both the per-lane random accesses of the shuffle and the row-wise write-out, where lanes walk
 // k, spread over the banks).  The int64 rows then leave as contiguous 512-byte stores -- the in-place global shuffle
 // above moved 13x the bytes of its result (every swap a read-modify-write of an 800-byte-strided line).
-constexpr int kPermStride = 66;
 __global__ __launch_bounds__(kWave) void k_rand_perms_lds(int64_t* __restrict__ perm, int64_t B, int64_t N, uint64_t seed,
                                                            int64_t env_offset) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -391,10 +390,6 @@ __global__ void k_tsp_2opt_reduce(int64_t N, int64_t B, int64_t slices, int64_t*
     best_j[b] = key >= 0 ? key % N : -1;
 }
 
-static inline bool dist_fits_lds(int64_t N, size_t extra) { return (size_t)N * N * 4 + extra <= (size_t)kLdsBytes - 1024; }
-
-static inline int tsp_block(int64_t N) { return N <= 256 ? kTspBlock : kTspBlockSmall; }
-
 static inline int tsp_grid(int64_t B, int block) {
     const int64_t waves = block / kWave;
     const int64_t cap = (int64_t)2 * 256 * kTspBlock / block;   // 32 waves per CU
@@ -413,9 +408,10 @@ int rls_tsp_tour_length(const float* dist, int64_t N, const int64_t* perm, int64
     RLS_REQUIRE(N > 0 && N < (1 << 30) && B >= 0, RLS_EINVAL, "bad sizes N=%lld B=%lld", (long long)N, (long long)B);
     if (B == 0) return RLS_OK;
     RLS_REQUIRE(dist && perm && length, RLS_EINVAL, "NULL pointer");
-    const dim3 grid(tsp_grid(B, tsp_block(N))), block(tsp_block(N));
-    if (dist_fits_lds(N, 0)) {
-        const size_t lds = (size_t)N * N * 4;
+    const TspForm f = tsp_plan_tour_length(N);
+    const dim3 grid(tsp_grid(B, f.block)), block(f.block);
+    if (f.lds_d) {
+        const size_t lds = f.lds;
         auto kern = k_tsp_tour_length<true>;
         if (lds > 64 * 1024) ensure_dyn_lds((const void*)kern, lds);
         hipLaunchKernelGGL(kern, grid, block, lds, as_stream(stream), dist, N, perm, B, length);
@@ -426,8 +422,25 @@ int rls_tsp_tour_length(const float* dist, int64_t N, const int64_t* perm, int64
 }
 
 int64_t rls_tsp_tables8_bytes(int64_t N, int32_t K) {
-    if (N < 3 || N > 256 || K < 1 || K >= N) return 0;
-    return (int64_t)((((size_t)N * K + 15) & ~(size_t)15) + (((size_t)N * (N - K - 1) + 15) & ~(size_t)15));
+    return (int64_t)tsp_tables8_size(N, K);
+}
+
+int rls_tsp_launch_form(int32_t what, int64_t N, int32_t K, int32_t has_tables8, rls_tsp_form* out) {
+    RLS_REQUIRE(out != nullptr, RLS_EINVAL, "out is NULL");
+    RLS_REQUIRE(N > 0 && N < (1 << 30), RLS_EINVAL, "bad size N=%lld", (long long)N);
+    TspForm f{};
+    switch (what) {
+        case RLS_TSP_TOUR_LENGTH: f = tsp_plan_tour_length(N); break;
+        case RLS_TSP_SWAP_DELTA: f = tsp_plan_swap_delta(N, K, has_tables8 != 0); break;
+        case RLS_TSP_STEP: f = tsp_plan_step(N); break;
+        case RLS_TSP_2OPT_BEST: f = tsp_plan_2opt_best(N, false); break;
+        case RLS_TSP_2OPT_BEST_EXACT: f = tsp_plan_2opt_best(N, true); break;
+        case RLS_TSP_RAND_PERMS: f = tsp_plan_rand_perms(N); break;
+        default: return fail(RLS_EINVAL, "unknown entry point what=%d", what);
+    }
+    if (f.err != RLS_OK) *out = rls_tsp_form{0, 0, 0, 0, 0, 0, 0};
+    else *out = rls_tsp_form{f.lds_d ? 1 : 0, f.tab8 ? 1 : 0, f.block, f.waves, (int64_t)f.lds, f.kernel, 1};
+    return RLS_OK;
 }
 
 int rls_tsp_swap_delta_all(const float* dist, int64_t N, const int64_t* perm, int64_t B, const int64_t* selected,
@@ -440,22 +453,20 @@ int rls_tsp_swap_delta_all(const float* dist, int64_t N, const int64_t* perm, in
     const bool draw = selected == nullptr;
     if (draw) {
         RLS_REQUIRE(nearest && random, RLS_EINVAL, "selected == NULL draws the partners in the kernel: nearest / random must be given");
-        RLS_REQUIRE(K >= 1 && K < N && random_stride >= N - K - 1, RLS_EINVAL, "bad neighbour tables K=%d stride=%d N=%lld", K,
-                    random_stride, (long long)N);
+        // (K = N - 1 leaves no far table to draw from: the reference's randint(0, N - K - 1) cannot run either)
+        RLS_REQUIRE(K >= 1 && K <= N - 2, RLS_EINVAL, "K=%d outside [1, N-2] (N=%lld): the in-kernel draw needs a far table", K, (long long)N);
+        RLS_REQUIRE(random_stride >= N - K - 1, RLS_EINVAL, "bad neighbour tables K=%d stride=%d N=%lld", K, random_stride, (long long)N);
     } else {
         RLS_REQUIRE(!selected_out, RLS_EINVAL, "selected_out is the in-kernel draw's record: it needs selected == NULL");
     }
-    const size_t tabs = (draw && tables8 && N <= 256) ? (size_t)rls_tsp_tables8_bytes(N, K) : 0;
     RLS_REQUIRE(!tables8 || (((uintptr_t)tables8) & 3) == 0, RLS_EINVAL, "tables8 must be 4-byte aligned");
-    const TspDraw dr{nearest, random, K, random_stride, near_threshold, seed, env_offset, selected_out, tables8, (int32_t)tabs};
-    const size_t scratch = (size_t)(tsp_block(N) / kWave) * 2 * N * 4;
-    RLS_REQUIRE(scratch <= (size_t)kLdsBytes - 1024, RLS_EUNSUPPORTED, "N=%lld too large for the per-wave tour scratch",
-                (long long)N);
-    const dim3 grid(tsp_grid(B, tsp_block(N))), block(tsp_block(N));
     // the neighbour tables as bytes in LDS when the ids fit a byte and they fit beside the matrix and the scratch
-    const bool tab8 = tabs > 0 && dist_fits_lds(N, scratch + tabs);
-    const bool in_lds = dist_fits_lds(N, scratch + (tab8 ? tabs : 0));
-    const size_t lds = (in_lds ? (size_t)N * N * 4 : 0) + scratch + (tab8 ? tabs : 0);
+    const TspForm f = tsp_plan_swap_delta(N, K, draw && tables8);
+    const TspDraw dr{nearest, random, K, random_stride, near_threshold, seed, env_offset, selected_out, tables8, (int32_t)f.tabs};
+    RLS_REQUIRE(f.err == RLS_OK, f.err, "N=%lld too large for the per-wave tour scratch", (long long)N);
+    const dim3 grid(tsp_grid(B, f.block)), block(f.block);
+    const bool tab8 = f.tab8, in_lds = f.lds_d;
+    const size_t lds = f.lds;
 #define LAUNCH_K13(LD, DRW)                                                                                              \
     do {                                                                                                                 \
         auto kern = (DRW && tab8) ? k_tsp_swap_delta_all<LD, DRW, true> : k_tsp_swap_delta_all<LD, DRW, false>;          \
@@ -494,16 +505,17 @@ int rls_tsp_2opt_best(const double* dist, int64_t N, const int64_t* perm, int64_
     RLS_REQUIRE(slices >= 1 && slices <= 65535, RLS_EINVAL, "slices=%d outside [1, 65535]", slices);
     if (B == 0) return RLS_OK;
     RLS_REQUIRE(dist && perm && best_i && best_j && best_value, RLS_EINVAL, "NULL pointer");
-    const size_t lds = 256 * 16 + (cur_length ? (size_t)(N + 1) * 8 : 0) + (size_t)N * 4;
-    RLS_REQUIRE(lds <= (size_t)kLdsBytes, RLS_EUNSUPPORTED, "N=%lld needs %zu B of LDS (max %d)", (long long)N, lds, kLdsBytes);
+    const TspForm f = tsp_plan_2opt_best(N, cur_length != nullptr);
+    const size_t lds = f.lds;
+    RLS_REQUIRE(f.err == RLS_OK, f.err, "N=%lld needs %zu B of LDS (max %d)", (long long)N, lds, kLdsBytes);
     if (cur_length) {
         auto kern = k_tsp_2opt_best<true>;
         if (lds > 64 * 1024) ensure_dyn_lds((const void*)kern, lds);
-        hipLaunchKernelGGL(kern, dim3((unsigned)B, (unsigned)slices), dim3(256), lds, as_stream(stream), dist, N, perm, B, cur_length, best_i, best_j, best_value);
+        hipLaunchKernelGGL(kern, dim3((unsigned)B, (unsigned)slices), dim3(f.block), lds, as_stream(stream), dist, N, perm, B, cur_length, best_i, best_j, best_value);
     } else {
         auto kern = k_tsp_2opt_best<false>;
         if (lds > 64 * 1024) ensure_dyn_lds((const void*)kern, lds);
-        hipLaunchKernelGGL(kern, dim3((unsigned)B, (unsigned)slices), dim3(256), lds, as_stream(stream), dist, N, perm, B, cur_length, best_i, best_j, best_value);
+        hipLaunchKernelGGL(kern, dim3((unsigned)B, (unsigned)slices), dim3(f.block), lds, as_stream(stream), dist, N, perm, B, cur_length, best_i, best_j, best_value);
     }
     if (slices > 1)
         hipLaunchKernelGGL(k_tsp_2opt_reduce, dim3((unsigned)ceil_div(B, 256)), dim3(256), 0, as_stream(stream), N, B, (int64_t)slices, best_i,
@@ -515,15 +527,16 @@ int rls_rand_perms(int64_t* perm, int64_t B, int64_t N, uint64_t seed, int64_t e
     RLS_REQUIRE(N > 0 && B >= 0, RLS_EINVAL, "bad sizes");
     if (B == 0) return RLS_OK;
     RLS_REQUIRE(perm, RLS_EINVAL, "perm is NULL");
-    const size_t lds = (size_t)N * kPermStride * sizeof(uint16_t);
-    if (N <= 65535 && lds <= (size_t)kLdsBytes / 2) {
+    const TspForm f = tsp_plan_rand_perms(N);
+    if (f.kernel == RLS_TSP_KERNEL_PERMS_LDS) {
+        const size_t lds = f.lds;
         auto kern = k_rand_perms_lds;
         if (lds > 64 * 1024) ensure_dyn_lds((const void*)kern, lds);
-        hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(B, kWave)), dim3(kWave), lds, as_stream(stream), perm, B, N, seed,
+        hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(B, kWave)), dim3(f.block), lds, as_stream(stream), perm, B, N, seed,
                            env_offset);
         return check_launch("k_rand_perms_lds");
     }
-    hipLaunchKernelGGL(k_rand_perms, dim3((unsigned)ceil_div(B, 256)), dim3(256), 0, as_stream(stream), perm, B, N,
+    hipLaunchKernelGGL(k_rand_perms, dim3((unsigned)ceil_div(B, f.block)), dim3(f.block), 0, as_stream(stream), perm, B, N,
                        seed, env_offset);
     return check_launch("k_rand_perms");
 }

@@ -7,6 +7,7 @@ from oracle import oracle_np as onp
 from rlsolver_amd import ops_mcpg_tsp as mops
 from rlsolver_amd.methods import MCPG as amcpg
 from tests.gpu_util import DEV, gnm_arr
+from tests.tsp_cases import isco_draw_np as _isco_draw_np
 
 pytestmark = pytest.mark.gpu
 
@@ -186,24 +187,6 @@ def test_tsp_golden(golden, name):
     dl = mops.tsp_2opt_delta(d, perms[dev(env)].contiguous(), dev(z[f"{name}/twoopt/i"]), dev(z[f"{name}/twoopt/j"]))
     np.testing.assert_allclose(dl.cpu().numpy(), z[f"{name}/twoopt/delta_f64"], rtol=1e-5,
                                atol=1e-5 * float(z[f"{name}/length_f32"].max()))
-
-
-def _isco_draw_np(seed, env, a, b, stream):
-    """The counter-based generator of the ISCO kernels (csrc/rls_draw.h: five murmur3 finalisers over seed, global env id, two
-    counters and a stream id) restated in numpy -- the SPEC the in-kernel partner draw of K13 is held to."""
-    M = np.uint64(0xFFFFFFFF)
-
-    def mix(h):
-        h = h ^ (h >> np.uint64(16)); h = (h * np.uint64(0x85EBCA6B)) & M
-        h = h ^ (h >> np.uint64(13)); h = (h * np.uint64(0xC2B2AE35)) & M
-        return h ^ (h >> np.uint64(16))
-    seed, env = np.uint64(seed), np.asarray(env, dtype=np.uint64)
-    a = np.asarray(a, dtype=np.uint64)
-    h = mix((seed & M) ^ np.uint64(0x9E3779B9))
-    h = mix(h ^ (seed >> np.uint64(32)))
-    h = mix(h ^ (env & M))
-    h = mix(h ^ (env >> np.uint64(32)) ^ ((a * np.uint64(0x9E3779B1)) & M))
-    return mix(h ^ np.uint64((b * 0x85EBCA77) & 0xFFFFFFFF) ^ np.uint64((stream * 0xC2B2AE3D) & 0xFFFFFFFF))
 
 
 @pytest.mark.parametrize("N,B,K", [(100, 1000, 20), (52, 130, 20), (7, 64, 3), (200, 70, 20), (300, 40, 20), (256, 33, 30)])

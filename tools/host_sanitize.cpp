@@ -15,6 +15,7 @@
 
 #include "rlsolver_hip.h"
 #include "rls_maxcut_plan.h"      // the MaxCut launch planner: host-only C++, so it runs under the sanitizers too
+#include "rls_tsp_plan.h"         // ... and the TSP one
 
 #include "../oracle/oracle.h"
 
@@ -265,6 +266,15 @@ static void run_planners(std::mt19937_64& rng) {
         CHECK(p.form == rls::PF_UNSUPPORTED ? p.err == RLS_EUNSUPPORTED && p.msg[0] != 0 : p.lds <= (size_t)rls::kLdsBytes && p.grid >= 1 && p.block >= 64,
               "plan form %d lds %zu grid %u block %u", p.form, p.lds, p.grid, p.block);
     rls_tuning_unset(nullptr);
+    // the TSP planner: sizes past every limit (the step's 10 240, K13's 5088), any K
+    const int64_t tn = 1 + (int64_t)(rng() % 12000);
+    const int32_t tk = (int32_t)(rng() % 300);
+    const rls::TspForm forms[] = {rls::tsp_plan_tour_length(tn), rls::tsp_plan_swap_delta(tn, tk, (f & 4096) != 0), rls::tsp_plan_step(tn),
+                                  rls::tsp_plan_2opt_best(tn * 4, (f & 8192) != 0), rls::tsp_plan_rand_perms(tn)};
+    for (const rls::TspForm& p : forms)
+        CHECK(p.err == RLS_EUNSUPPORTED || (p.err == RLS_OK && p.lds <= (size_t)rls::kLdsBytes && p.block >= 64 && p.waves * 64 == p.block &&
+                                            (!p.tab8 || p.lds_d)),
+              "TSP form N %lld K %d err %d lds %zu block %d waves %d", (long long)tn, tk, p.err, p.lds, p.block, p.waves);
 }
 
 int main(int argc, char** argv) {
