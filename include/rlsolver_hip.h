@@ -708,6 +708,59 @@ int rls_qubo_sparse_local_search_value(const int32_t* rowptr, const int32_t* col
  * nnz = 0 -- the sparse one with a level schedule built over the symmetrised pattern (Q_ij != 0 or Q_ji != 0). */
 int rls_qubo_local_search_supported(int64_t n, int64_t C, int32_t form);
 
+/* ------------------------------------------------------------------ MaxSAT */
+
+/* [host] Level schedule of mcpg_sampling_maxsat's sweep  methods/MCPG/sampling.py:259-271 (additive: the ABI stays v12).
+ * The formula is a clause CSR: clause_ptr int32 [M + 1], lit int32 [L] signed +-(v + 1), weight int32 [M] (>= 1) or NULL = all
+ * ones; order int32 [nvar] = the visiting order (ndata[3]).  For variable i the reference lists, once per OCCURRENCE of i, the
+ * whole clause the occurrence sits in (dataloader.py:240-247: a clause that holds i twice is listed twice) and keeps the flip
+ * where  sum_listed max_lit(s_v neg)  grows, a uniform draw deciding only ties (new - old is an even integer).  A listed clause
+ * moves that sum by +-2w when no literal of ANOTHER variable satisfies it and i's own literals in it have one sign; so with
+ * crit = ~OR_others (x_v ^ sign), make = weight of the critical clauses whose own literal is false, break = of those whose own
+ * literal is true, the rule is  x_i ^= [make > break] | ([make == break] & coin).
+ * level(position) = 1 + the highest level of an earlier-visited variable that shares a clause with it: the variables of a level
+ * share no clause, so deciding level after level from the pre-level state is the sequential sweep.  Positions are sorted by
+ * (level, stream length descending) and cut into groups of 64 LANES, lane = variable.
+ * lv_ptr [host, groups + 1]: (record offset / 64) | planes << 24 | weighted << 30 | first group of a level << 31; planes = counter
+ * planes the group's largest listed weight sum needs (1 .. 24).  Group record in lv_data:
+ *     64 x 2 words   lane l: variable (nvar on idle lanes), visiting position (keys the coin)
+ *     per block of 4 rounds, [64 lanes][4 rounds] (a lane fetches a block in one 16-byte load), round r of lane l at
+ *     128 + B (r / 4) + 4 l + r % 4, B = 256:   8 v | sign << 31 | ends << 0 | class << 1
+ *         = one literal of another variable of the listed clause (8 v = byte offset of its word in the LDS tile; sign = negated);
+ *           `ends` marks the clause's last entry and carries the variable's own sign class in it (1 positive, 2 negative, 3 both:
+ *           the clause cannot change).  A clause without other literals, and one of class 3, is the single entry 8 nvar | ends |
+ *           class (word nvar of the tile is zero); so is padding (8 nvar, ends = 0).
+ *     weighted (weight != NULL): B = 512 and the block's second half holds the weights, that of a clause beside its last entry.
+ * The table ends in 512 spare words (a lane requests its next block unguarded).  NULL outputs: sizing (*num_groups, *total).
+ * A stream is never split over lanes: a variable of 600 clauses costs its group 600+ rounds.
+ * Limits (rls_maxsat_local_search_supported): nvar <= 20 445 (8 bytes per variable and the zero word + 272 bytes of tables in 160 KB of LDS); the
+ * sum of all clause weights, and of the weights listed for one variable, below 2^24 (the reference's own exact float32 range):
+ * RLS_EUNSUPPORTED beyond.  A literal 0 or past nvar, a weight < 1, an order that is no permutation: RLS_EINVAL. */
+int rls_maxsat_visit_levels(const int32_t* clause_ptr, const int32_t* lit, const int32_t* weight, int64_t nvar, int64_t M,
+                            const int32_t* order, int32_t* lv_ptr, int64_t ptr_capacity, int32_t* lv_data, int64_t data_capacity,
+                            int64_t* num_groups, int64_t* total);
+
+/* [host] 1 when the MaxSAT sampler covers nvar variables and clause weights that sum to weight_sum, else 0; the limits themselves
+ * go to *max_nvar / *max_weight_sum (largest accepted values; either may be NULL). */
+int rls_maxsat_local_search_supported(int64_t nvar, int64_t weight_sum, int64_t* max_nvar, int64_t* max_weight_sum);
+
+/* The sweep and the score of mcpg_sampling_maxsat  methods/MCPG/sampling.py:257-274 in ONE kernel, one workgroup per 64-chain
+ * tile, the tile uint64 [nvar] in LDS, every operation 64 chains wide in one lane, make / break in bit-sliced counters.
+ * xs_in: bit-packed chains holding 0|1 (the sampler maps them to -1|+1), C_in as in rls_mcpg_metro_rounds; xs_out: bit-packed
+ * (out_spin_bytes = 0; may alias xs_in when C_in == C) or float32 node-major [nvar, C] (4).  num_ls passes over the schedule of
+ * rls_maxsat_visit_levels (lv_ptr / lv_data on the device); num_ls = 0: the pure scorer.  Tie coins: counter hash keyed by
+ * (seed, GLOBAL 64-chain block [chain_ids, as rls_mcpg_local_search_levels], pass, position), or coins uint64
+ * [num_ls * nvar, ceil(C / 64)] -- bit c % 64 of word [pass * nvar + pos, c / 64] = "u < 1/2" for chain c (tests).
+ * Then expected[c] = -S[c], S = sum over the clauses of the CSR (device: clause_ptr [M + 1], lit, weight or NULL) of
+ * max_lit(s_v neg) = +w for a satisfied clause, -w for an unsatisfied one, 0 for an empty one (:272-274).  The reference's
+ * res = (S + K) / 2 is rls_mcpg_pick_best's (num_edges - expected) / 2 with num_edges := K, its first argmax of res that
+ * kernel's first argmin of expected: K never enters this launch.  lit must not be NULL when M > 0, also where every clause is
+ * empty (it is then never read). */
+int rls_maxsat_local_search(const void* xs_in, int64_t C_in, void* xs_out, int out_spin_bytes, int64_t C, int64_t nvar,
+                            const int32_t* lv_ptr, const int32_t* lv_data, int64_t num_groups, int64_t num_ls,
+                            const uint64_t* coins, uint64_t seed, const int32_t* clause_ptr, const int32_t* lit,
+                            const int32_t* weight, int64_t M, float* expected, const rls_chain_ids* chain_ids, void* stream);
+
 /* --------------------------------------------------------------------- TSP */
 
 /* K12 ISCO_TSP.calculate_distance(sample)  envs/env_ISCO.py:346-350.

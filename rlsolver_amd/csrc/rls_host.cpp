@@ -493,6 +493,164 @@ int rls_mcpg_visit_levels(const int32_t* rowptr, const int32_t* col, int64_t N, 
     return RLS_OK;
 }
 
+// ---- MaxSAT: level schedule of the sampler's sweep (include/rlsolver_hip.h: rls_maxsat_visit_levels)
+namespace rls {
+constexpr int64_t kMaxsatMaxVars = (kLdsBytes - 272) / 8 - 1;     // tile + the zero word + 65 score slots in 160 KB
+constexpr int64_t kMaxsatMaxWeight = (1 << 24) - 1;
+}
+
+int rls_maxsat_local_search_supported(int64_t nvar, int64_t weight_sum, int64_t* max_nvar, int64_t* max_weight_sum) {
+    if (max_nvar) *max_nvar = rls::kMaxsatMaxVars;
+    if (max_weight_sum) *max_weight_sum = rls::kMaxsatMaxWeight;
+    return nvar >= 1 && nvar <= rls::kMaxsatMaxVars && weight_sum >= 0 && weight_sum <= rls::kMaxsatMaxWeight;
+}
+
+int rls_maxsat_visit_levels(const int32_t* clause_ptr, const int32_t* lit, const int32_t* weight, int64_t nvar, int64_t M,
+                            const int32_t* order, int32_t* lv_ptr, int64_t ptr_capacity, int32_t* lv_data, int64_t data_capacity,
+                            int64_t* num_groups, int64_t* total) {
+    if (!clause_ptr || !order || nvar < 1 || M < 0 || !num_groups || !total || clause_ptr[0] != 0)
+        return rls::fail(RLS_EINVAL, "rls_maxsat_visit_levels: bad arguments");
+    if (nvar > rls::kMaxsatMaxVars)
+        return rls::fail(RLS_EUNSUPPORTED, "rls_maxsat_visit_levels: nvar=%lld, the 64-chain tile holds at most %lld variables in LDS",
+                         (long long)nvar, (long long)rls::kMaxsatMaxVars);
+    if (lv_data && !lv_ptr) return rls::fail(RLS_EINVAL, "rls_maxsat_visit_levels: lv_data without lv_ptr");
+    const int64_t L = clause_ptr[M];
+    if (L > 0 && !lit) return rls::fail(RLS_EINVAL, "rls_maxsat_visit_levels: lit is NULL");
+    int64_t wsum = 0;
+    for (int64_t c = 0; c < M; ++c) {
+        if (clause_ptr[c + 1] < clause_ptr[c]) return rls::fail(RLS_EINVAL, "rls_maxsat_visit_levels: clause_ptr decreases at clause %lld", (long long)c);
+        if (weight && weight[c] < 1) return rls::fail(RLS_EINVAL, "rls_maxsat_visit_levels: clause %lld has weight %d < 1", (long long)c, weight[c]);
+        wsum += weight ? weight[c] : 1;
+    }
+    if (wsum > rls::kMaxsatMaxWeight)
+        return rls::fail(RLS_EUNSUPPORTED, "rls_maxsat_visit_levels: the clause weights sum to %lld, the limit is %lld (exact float32 range)",
+                         (long long)wsum, (long long)rls::kMaxsatMaxWeight);
+    std::vector<int32_t> pos_of((size_t)nvar, -1);
+    for (int64_t p = 0; p < nvar; ++p) {
+        if (order[p] < 0 || order[p] >= nvar || pos_of[(size_t)order[p]] != -1)
+            return rls::fail(RLS_EINVAL, "rls_maxsat_visit_levels: order is not a permutation");
+        pos_of[(size_t)order[p]] = (int32_t)p;
+    }
+    // occurrences per variable, in clause order: one listed clause each
+    std::vector<int64_t> occ_ptr((size_t)nvar + 1, 0);
+    for (int64_t k = 0; k < L; ++k) {
+        const int64_t l = lit[k];
+        if (l == 0 || l > nvar || -l > nvar)
+            return rls::fail(RLS_EINVAL, "rls_maxsat_visit_levels: literal %lld outside +-[1, %lld]", (long long)l, (long long)nvar);
+        ++occ_ptr[(size_t)((l < 0 ? -l : l) - 1) + 1];
+    }
+    for (int64_t v = 0; v < nvar; ++v) occ_ptr[(size_t)v + 1] += occ_ptr[(size_t)v];
+    std::vector<int32_t> occ((size_t)(L > 0 ? L : 1));
+    {
+        std::vector<int64_t> fill(occ_ptr.begin(), occ_ptr.end() - 1);
+        for (int64_t c = 0; c < M; ++c)
+            for (int32_t k = clause_ptr[c]; k < clause_ptr[c + 1]; ++k) occ[(size_t)fill[(size_t)(std::abs(lit[k]) - 1)]++] = (int32_t)c;
+    }
+    // levels over visiting positions; per position: entries of its stream and the weight it lists
+    std::vector<int32_t> level((size_t)nvar), clause_lev((size_t)(M > 0 ? M : 1), 0), len((size_t)nvar);
+    std::vector<int64_t> listed((size_t)nvar);
+    for (int64_t p = 0; p < nvar; ++p) {
+        const int32_t i = order[p];
+        int32_t l = 0, n = 0;
+        int64_t w = 0;
+        for (int64_t o = occ_ptr[(size_t)i]; o < occ_ptr[(size_t)i + 1]; ++o) {
+            const int32_t c = occ[(size_t)o];
+            if (clause_lev[(size_t)c] > l) l = clause_lev[(size_t)c];
+            bool pos = false, neg = false;
+            int32_t others = 0;
+            for (int32_t k = clause_ptr[c]; k < clause_ptr[c + 1]; ++k) {
+                if (std::abs(lit[k]) - 1 == i) (lit[k] > 0 ? pos : neg) = true;
+                else ++others;
+            }
+            n += (pos && neg) || others == 0 ? 1 : others;
+            w += weight ? weight[c] : 1;
+        }
+        ++l;
+        for (int64_t o = occ_ptr[(size_t)i]; o < occ_ptr[(size_t)i + 1]; ++o)
+            if (clause_lev[(size_t)occ[(size_t)o]] < l) clause_lev[(size_t)occ[(size_t)o]] = l;
+        if (w > rls::kMaxsatMaxWeight)
+            return rls::fail(RLS_EUNSUPPORTED, "rls_maxsat_visit_levels: the clauses listed for variable %d weigh %lld, the limit is %lld",
+                             i, (long long)w, (long long)rls::kMaxsatMaxWeight);
+        level[(size_t)p] = l;
+        len[(size_t)p] = n;
+        listed[(size_t)p] = w;
+    }
+    std::vector<int32_t> sp((size_t)nvar);
+    for (int64_t p = 0; p < nvar; ++p) sp[(size_t)p] = (int32_t)p;
+    std::stable_sort(sp.begin(), sp.end(), [&](int32_t a, int32_t b) {
+        if (level[(size_t)a] != level[(size_t)b]) return level[(size_t)a] < level[(size_t)b];
+        return len[(size_t)a] > len[(size_t)b];
+    });
+    const int64_t blk = weight ? 512 : 256, pad = nvar * 8;
+    int64_t ng = 0, off = 0;
+    for (int64_t k0 = 0; k0 < nvar;) {
+        int64_t k1 = k0 + 1;
+        while (k1 < nvar && k1 - k0 < 64 && level[(size_t)sp[(size_t)k1]] == level[(size_t)sp[(size_t)k0]]) ++k1;
+        const bool level_start = k0 == 0 || level[(size_t)sp[(size_t)k0 - 1]] != level[(size_t)sp[(size_t)k0]];
+        const int64_t blocks = (len[(size_t)sp[(size_t)k0]] + 3) / 4;          // the longest stream of the group comes first
+        int64_t wmax = 1;
+        for (int64_t k = k0; k < k1; ++k) wmax = std::max(wmax, listed[(size_t)sp[(size_t)k]]);
+        int32_t planes = 1;
+        while ((wmax >> planes) != 0) ++planes;
+        const int64_t reclen = 128 + blocks * blk;
+        if ((off + reclen) / 64 >= (1 << 24)) return rls::fail(RLS_EUNSUPPORTED, "rls_maxsat_visit_levels: schedule too large");
+        if (lv_ptr) {
+            if (ng + 1 >= ptr_capacity) return rls::fail(RLS_EINVAL, "rls_maxsat_visit_levels: ptr capacity too small");
+            lv_ptr[ng] = (int32_t)((uint32_t)(off / 64) | ((uint32_t)planes << 24) | (weight ? 0x40000000u : 0u) | (level_start ? 0x80000000u : 0u));
+        }
+        if (lv_data) {
+            if (off + reclen > data_capacity) return rls::fail(RLS_EINVAL, "rls_maxsat_visit_levels: data capacity too small");
+            int32_t* rec = lv_data + off;
+            for (int64_t l = 0; l < 64; ++l) rec[2 * l] = (int32_t)nvar, rec[2 * l + 1] = 0;
+            for (int64_t b = 0; b < blocks; ++b)
+                for (int64_t e = 0; e < blk; ++e) rec[128 + b * blk + e] = e < 256 ? (int32_t)pad : 0;
+            for (int64_t k = k0; k < k1; ++k) {
+                const int64_t ln = k - k0;
+                const int32_t p = sp[(size_t)k], i = order[p];
+                rec[2 * ln] = i;
+                rec[2 * ln + 1] = p;
+                int64_t r = 0;
+                auto put = [&](uint32_t e, int32_t w) {
+                    const int64_t at = 128 + (r / 4) * blk + 4 * ln + r % 4;
+                    rec[at] = (int32_t)e;
+                    if (weight) rec[at + 256] = w;
+                    ++r;
+                };
+                for (int64_t o = occ_ptr[(size_t)i]; o < occ_ptr[(size_t)i + 1]; ++o) {
+                    const int32_t c = occ[(size_t)o], w = weight ? weight[c] : 1;
+                    bool pos = false, neg = false;
+                    int32_t others = 0;
+                    for (int32_t q = clause_ptr[c]; q < clause_ptr[c + 1]; ++q) {
+                        if (std::abs(lit[q]) - 1 == i) (lit[q] > 0 ? pos : neg) = true;
+                        else ++others;
+                    }
+                    const uint32_t tag = 1u | ((pos ? 1u : 0u) | (neg ? 2u : 0u)) << 1;
+                    if ((pos && neg) || others == 0) { put((uint32_t)pad | tag, w); continue; }
+                    for (int32_t q = clause_ptr[c]; q < clause_ptr[c + 1]; ++q) {
+                        if (std::abs(lit[q]) - 1 == i) continue;
+                        --others;
+                        put((uint32_t)(std::abs(lit[q]) - 1) * 8u | (lit[q] < 0 ? 0x80000000u : 0u) | (others == 0 ? tag : 0u), others == 0 ? w : 0);
+                    }
+                }
+            }
+        }
+        off += reclen;
+        ++ng;
+        k0 = k1;
+    }
+    if (lv_ptr) {
+        if (ng >= ptr_capacity) return rls::fail(RLS_EINVAL, "rls_maxsat_visit_levels: ptr capacity too small");
+        lv_ptr[ng] = (int32_t)(off / 64);
+    }
+    if (lv_data) {
+        if (off + 512 > data_capacity) return rls::fail(RLS_EINVAL, "rls_maxsat_visit_levels: data capacity too small");
+        for (int64_t e = 0; e < 512; ++e) lv_data[off + e] = (int32_t)pad;
+    }
+    *num_groups = ng;
+    *total = off + 512;
+    return RLS_OK;
+}
+
 int rls_graph_ell(const int32_t* rowptr, const int32_t* col, int64_t N, int32_t* ell_ptr, int32_t* ell,
                   int64_t capacity, int64_t* total) {
     if (!rowptr || !ell_ptr || N < 0 || (N > 0 && rowptr[N] > 0 && !col))

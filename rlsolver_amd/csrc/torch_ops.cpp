@@ -651,6 +651,40 @@ void mcpg_local_search_levels(int64_t g, const Tensor& xs_in, int64_t C_in, Tens
                                     lv_ptr.numel() - 1, num_ls, (const uint64_t*)p(coins), (uint64_t)seed, (float*)p(expected), cid.ptr(), cur_stream(xs_in)),
        "rls_mcpg_local_search_levels");
 }
+void maxsat_local_search(const Tensor& xs_in, int64_t C_in, Tensor xs_out, int64_t C, const Tensor& lv_ptr, const Tensor& lv_data, int64_t num_ls,
+                         const OptTensor& coins, int64_t seed, const Tensor& clause_ptr, const Tensor& lit, const OptTensor& weight,
+                         Tensor expected, int64_t chain_offset, int64_t chain_period, int64_t chain_skip) {
+    const ChainIdsArg cid(chain_offset, chain_period, chain_skip);
+    dev(xs_in, "xs_in", I64);
+    TORCH_CHECK(xs_in.dim() == 2, "xs_in must be bit-packed chains [ceil(C_in / 64), nvar]");
+    const int64_t nvar = xs_in.size(1);
+    chain_shape(xs_in, 0, nvar, C_in > 0 ? C_in : C, "xs_in");
+    const int osb = chain_bytes(xs_out, "xs_out");
+    TORCH_CHECK(osb == 0 || osb == 4, "xs_out must be float32 node-major or bit-packed");
+    chain_shape(xs_out, osb, nvar, C, "xs_out");
+    same_device(xs_in, xs_out, "xs_out");
+    dev(lv_ptr, "lv_ptr", I32);
+    dev(lv_data, "lv_data", I32);
+    TORCH_CHECK(lv_ptr.numel() >= 2, "lv_ptr must hold groups + 1 offsets");
+    TORCH_CHECK(num_ls >= 0, "num_ls must be >= 0");
+    optdev(coins, "coins", I64);
+    if (coins.has_value()) shape2(*coins, "coins", num_ls * nvar, (C + 63) / 64);
+    dev(clause_ptr, "clause_ptr", I32);
+    dev(lit, "lit", I32);
+    TORCH_CHECK(clause_ptr.dim() == 1 && clause_ptr.numel() >= 1, "clause_ptr must be [M + 1]");
+    const int64_t M = clause_ptr.numel() - 1;
+    TORCH_CHECK(lit.dim() == 1, "lit must be 1-D");
+    optdev(weight, "weight", I32);
+    if (weight.has_value()) count(*weight, "weight", M);
+    dev(expected, "expected", F32);
+    count(expected, "expected", C);
+    for (const Tensor* t : {&lv_ptr, &lv_data, &clause_ptr, &lit, (const Tensor*)&expected}) same_device(xs_in, *t, "every tensor");
+    RLS_GUARD(xs_in);
+    ok(rls_maxsat_local_search(p(xs_in), C_in, p(xs_out), osb, C, nvar, (const int32_t*)p(lv_ptr), (const int32_t*)p(lv_data), lv_ptr.numel() - 1,
+                               num_ls, (const uint64_t*)p(coins), (uint64_t)seed, (const int32_t*)p(clause_ptr), (const int32_t*)p(lit),
+                               (const int32_t*)p(weight), M, (float*)p(expected), cid.ptr(), cur_stream(xs_in)),
+       "rls_maxsat_local_search");
+}
 void mcpg_pick_best(const Tensor& expected, const Tensor& xs, int64_t N, int64_t total_mcmc_num, int64_t repeat_times, int64_t num_edges,
                     Tensor best_index, Tensor vs_good, Tensor xs_good) {
     dev(expected, "expected", F32);
@@ -1011,6 +1045,8 @@ TORCH_LIBRARY(rlsolver_hip, m) {
     m.def("tsp_2opt_best(Tensor dist, Tensor perm, Tensor? cur_length, Tensor(a!) best_i, Tensor(b!) best_j, Tensor(c!) best_value) -> ()");
     m.def("isco_maxcut_step(int graph, Tensor x, Tensor(a!) y_out, Tensor path_length, float temperature, Tensor? u_gumbel, Tensor? u_accept, "
           "int seed, int env_offset, Tensor(b!)? energy_out, Tensor(c!)? acc_out, Tensor(d!)? terms_out, Tensor(e!)? mask_out, Tensor(f!)? scratch=None) -> ()");
+    m.def("maxsat_local_search(Tensor xs_in, int C_in, Tensor(a!) xs_out, int C, Tensor lv_ptr, Tensor lv_data, int num_ls, Tensor? coins, "
+          "int seed, Tensor clause_ptr, Tensor lit, Tensor? weight, Tensor(b!) expected, int chain_offset=0, int chain_period=0, int chain_skip=0) -> ()");
     m.def("isco_mis_step(int graph, Tensor x, Tensor(a!) y_out, Tensor path_length, float temperature, float lam, Tensor? u_gumbel, Tensor? u_accept, "
           "int seed, int env_offset, Tensor(b!)? energy_out, Tensor(c!)? acc_out, Tensor(d!)? terms_out, Tensor(e!)? mask_out, Tensor(f!)? scratch=None) -> ()");
     m.def("isco_tsp_step(Tensor dist, Tensor nearest, float near_threshold, Tensor random, Tensor perm_in, Tensor(a!) perm_out, int path_length, "
@@ -1069,5 +1105,6 @@ TORCH_LIBRARY_IMPL(rlsolver_hip, CUDA, m) {   // "CUDA" is the HIP dispatch key 
     m.impl("tsp_2opt_best", &tsp_2opt_best);
     m.impl("isco_maxcut_step", &isco_maxcut_step);
     m.impl("isco_mis_step", &isco_mis_step);
+    m.impl("maxsat_local_search", &maxsat_local_search);
     m.impl("isco_tsp_step", &isco_tsp_step);
 }

@@ -363,6 +363,16 @@ def sampler_func(data, xs_sample: TEN, num_ls: int, total_mcmc_num: int, repeat_
     return vs_good, xs_good, value
 
 
+def _round_local_search(data, samples: PackedChains, num_ls: int, seed: int, out: PackedChains, chain_ids):
+    """The sweep + score of one round, by problem family: a data object that brings its own (``round_local_search``:
+    Data_MaxSAT, methods/MCPG_maxsat.py) runs it, every other one is a MaxCut graph on the level-parallel K7.
+    Returns (chains after the sweep, expected f32 [C])."""
+    own = getattr(data, "round_local_search", None)
+    if own is not None:
+        return own(samples, num_ls, seed, out, chain_ids)
+    return mops.mcpg_local_search_levels(data.graph, samples, data._lv_ptr, data._lv_data, num_ls, seed, out=out, chain_ids=chain_ids)
+
+
 class _ReturnFn(torch.autograd.Function):
     """get_return (MCPG.py:292-302) with the samples bit-packed: objective = mean_c(log_prob_sum_c * value_c) where
     log_prob_sum_c = sum_n log(s p + (1 - s)(1 - p)).  Forward and backward need only A_n = sum_c value_c s_nc
@@ -455,6 +465,8 @@ class MCPGRound(Sharded):
         # the bit-packed walk keeps a 32 KB window of draws beside the tile: up to N ~ 16 000.  Beyond (G81: 20 000 nodes) the round
         # runs on the node-major kernels through the f32 surface and packs what it keeps
         self._nodemajor = mops.mcpg_metro_max_rounds(self.N, 0) == 0
+        if self._nodemajor and getattr(data, "round_local_search", None) is not None:
+            raise NotImplementedError("this problem family runs on the bit-packed walk only (N <= ~16 000)")
         if self._nodemajor and self.sharded:
             raise NotImplementedError("a sharded MCPGRound needs the bit-packed walk (N <= ~16 000)")
         if self.sharded and self.now_max_res.numel():
@@ -466,6 +478,12 @@ class MCPGRound(Sharded):
                 raise ValueError("a sharded MCPGRound exchanges its incumbents as integer MAXLOC keys: now_max_res must hold integers "
                                  "or half-integers below 2^42 in magnitude (cut values of an integer-weighted graph); run graphs "
                                  "with non-integer weights unsharded")
+
+    def _scaled(self, value: TEN) -> TEN:
+        """``value`` in the units of the family's result: MaxSAT's res = (S + K) / 2 moves half as fast as its ``expected`` = -S
+        (``value_scale`` of the data object); a MaxCut graph has none and the tensor passes through untouched."""
+        scale = getattr(self.data, "value_scale", None)
+        return value if scale is None else value * scale
 
     def _global_best(self, values: TEN, rows: Optional[PackedChains], maximize: bool):
         """(best value 0-dim, GLOBAL index 0-dim int64, its chain bool [N] or None) over every rank's ``values``; first index on
@@ -511,17 +529,16 @@ class MCPGRound(Sharded):
         Cg = self.M_total * self.R
         metro_sampling_packed(xs_prob, self.start, self.change_times, num_chains=C, out=self.samples, seed=self._next_seed(),
                               chain_ids=self.chain_ids, stats=self if self.sharded else None, total_chains=Cg)
-        xs_loc, expected = mops.mcpg_local_search_levels(self.data.graph, self.samples, self.data._lv_ptr, self.data._lv_data,
-                                                         self.num_ls, self._next_seed(), out=self.work, chain_ids=self.chain_ids)
+        xs_loc, expected = _round_local_search(self.data, self.samples, self.num_ls, self._next_seed(), self.work, self.chain_ids)
         _, temp_max, temp_info = mops.mcpg_pick_best(expected, xs_loc, self.M, self.R, self.data.num_edges)
         if not self.sharded:
             self.best_value, self.best_index = mops.mcpg_merge_best(temp_max, temp_info, self.now_max_res, self.now_max_info)
-            self.value = expected - expected.mean()
+            self.value = self._scaled(expected - expected.mean())
         else:
             mops.mcpg_merge_best(temp_max, temp_info, self.now_max_res, self.now_max_info, replace_worst=False)
             self._replace_global_worst(temp_info)
             total = self._global_sum(expected.sum(dtype=torch.float64).reshape(1))          # the mean over the whole batch (:165)
-            self.value = expected - (total[0] / Cg).to(torch.float32)
+            self.value = self._scaled(expected - (total[0] / Cg).to(torch.float32))
         self.expected = expected
         self.start = temp_info
         self._sums = None
@@ -559,7 +576,7 @@ def run_mcpg(data, xs_init: TEN, vs_init: TEN, total_mcmc_num: int, repeat_times
     ``kept_offset`` / ``total_kept`` / ``group``: this process runs a shard of the kept chains (see MCPGRound); value, best x
     and the policy are those of the whole batch on every rank."""
     import time
-    device = data.graph.device
+    device = data.device if hasattr(data, "device") else data.graph.device      # (a MaxCut graph / a Data_MaxSAT)
     rnd = MCPGRound(data, xs_init, vs_init, total_mcmc_num, repeat_times, num_ls, kept_offset=kept_offset,
                     total_kept=total_kept, group=group, seed=seed)
     lin = torch.nn.Parameter(torch.zeros(data.num_nodes, device=device))

@@ -190,6 +190,37 @@ def mcpg_local_search_levels(g: DeviceGraph, xs_in, lv_ptr: TEN, lv_data: TEN, n
     return xs_out, expected
 
 
+def mcpg_maxsat_local_search(xs_in: PackedChains, lv_ptr: TEN, lv_data: TEN, clause_ptr: TEN, lit: TEN, weight: Optional[TEN],
+                             num_ls: int, seed: int = 0, coins: Optional[TEN] = None, out=None, num_chains: Optional[int] = None,
+                             chain_ids=None):
+    """The sweep and the score of the MaxSAT sampler (include/rlsolver_hip.h: rls_maxsat_local_search) on the schedule of
+    rls_maxsat_visit_levels.  ``xs_in``: PackedChains over the variables (may hold fewer chains than ``num_chains``, a multiple of
+    64: broadcast); ``clause_ptr`` / ``lit`` / ``weight``: the formula as a clause CSR, int32 on the device; ``coins`` int64
+    [num_ls * nvar, ceil(C / 64)]: the tie coins "u < 1/2" -- test hook; None = counter hash keyed by seed.  ``out``: a PackedChains
+    to write (may be xs_in itself) or None = node-major f32.  ``num_ls = 0`` only scores.
+    Returns (xs_out, expected f32 [C]) with expected = -sum_clauses max_lit(s_v neg)."""
+    if not isinstance(xs_in, PackedChains):
+        raise TypeError("xs_in must be a PackedChains")
+    dev, N = xs_in.device, xs_in.num_nodes
+    Cc = xs_in.num_chains if num_chains is None else num_chains
+    for t, name in ((lv_ptr, "lv_ptr"), (lv_data, "lv_data"), (clause_ptr, "clause_ptr"), (lit, "lit")):
+        _check(t, name, (torch.int32,), dev)
+    if weight is not None:
+        _check(weight, "weight", (torch.int32,), dev, (clause_ptr.numel() - 1,))
+    if coins is not None:
+        _check(coins, "coins", (torch.int64,), dev, (num_ls * N, (Cc + 63) // 64))
+    if out is None:
+        xs_out = ot = torch.empty((N, Cc), dtype=torch.float32, device=dev)
+    else:
+        if not isinstance(out, PackedChains) or out.num_chains != Cc or out.num_nodes != N or out.device != dev:
+            raise ValueError("out must be a PackedChains of num_chains chains")
+        xs_out, ot = out, out.words
+    expected = torch.empty(Cc, dtype=torch.float32, device=dev)
+    _t.maxsat_local_search(xs_in.words, xs_in.num_chains, ot, Cc, lv_ptr, lv_data, int(num_ls), coins, _s64(seed), clause_ptr, lit, weight,
+                           expected, *_chain_ids(chain_ids))
+    return xs_out, expected
+
+
 def mcpg_pick_best(expected: TEN, xs, total_mcmc_num: int, repeat_times: int, num_edges: int):
     """K8 second half.  Returns (best_index int64 [M], vs_good f32 [M], xs_good: f32 [N, M] or PackedChains of M chains)."""
     st, sb, N, Cc = _chains(xs, "xs")

@@ -1692,7 +1692,98 @@ def gen_graph_forms():
     save("maxcut_graph_forms", **out)
 
 
-ALL = {"graph_forms": gen_graph_forms, "mcpg_weighted": gen_mcpg_weighted, "isco_steps": gen_isco_steps, "isco_mis": gen_isco_mis, "spinsystem_cpu": gen_spinsystem_cpu, "spinsystem": gen_spinsystem, "spinsystem_perenv": gen_spinsystem_perenv, "qubo": gen_qubo, "qubo_asym": gen_qubo_asym, "isco_maxcut": gen_isco_maxcut, "maxcut": gen_maxcut, "sweep": gen_sweep, "lsclass": gen_local_search_class, "ppo": gen_ppo,
+def maxsat_fixture_texts():
+    """The formulas of tests/golden/maxsat.npz as (.cnf | .wcnf) texts with their sampler parameters (M kept chains, R repeats,
+    num_ls, change_times); seeded, so the fixture regenerates byte-identically."""
+    rng = np.random.RandomState(4711)
+
+    def three(nvar, n, hub=None):
+        out = []
+        for _ in range(n):
+            vs = rng.choice(np.arange(2 if hub else 1, nvar + 1), size=2 if hub else 3, replace=False).tolist() + ([hub] if hub else [])
+            out.append([int(v) * (1 if rng.rand() < 0.5 else -1) for v in vs])
+        return out
+
+    def cnf(nvar, clauses, nclause=None):
+        return f"c generated\np cnf {nvar} {len(clauses) if nclause is None else nclause}\n" + "".join(
+            " ".join(map(str, cl + [0])) + "\n" for cl in clauses)
+
+    long40 = [int(v) * (1 if v % 3 else -1) for v in range(1, 41)]
+    edge = [[1, 1, 2], [3, -3, 4], [], [5], [-6], [7], long40, [-1, 2, -2, 8], [9, 9, 9]] + three(44, 20)
+    wc = [(3, [1]), (1, [-1]), (1, [-1]), (1, [-1]), (20, [2, -3]), (20, [4]), (3, [-4, 5]), (1, [5, 5, -6])]
+    for _ in range(24):
+        vs = rng.choice(np.arange(1, 13), size=rng.randint(1, 4), replace=False).tolist()
+        wc.append((int(rng.choice([1, 3, 20])), [int(v) * (1 if rng.rand() < 0.5 else -1) for v in vs]))
+    wtext = f"p wcnf 12 {len(wc)} 20\n" + "".join(" ".join(map(str, [w] + cl + [0])) + "\n" for w, cl in wc)
+    return {
+        "edge": (".cnf", cnf(45, edge, len(edge) + 3), 4, 2, 2, 4),
+        "rand70": (".cnf", cnf(70, three(70, 300)), 4, 4, 2, 7),
+        "wcnf": (".wcnf", wtext, 4, 2, 2, 2),
+        "hub": (".cnf", cnf(50, three(50, 600, hub=1)), 8, 1, 1, 5),
+        "one_empty": (".cnf", "p cnf 1 0\n", 2, 2, 1, 1),
+        "one_unit": (".cnf", "p cnf 1 1\n1 0\n", 2, 2, 1, 1),
+    }
+
+
+def gen_maxsat():
+    """maxsat_dataloader (rlsolver/methods/MCPG/dataloader.py:169-266) and mcpg_sampling_maxsat (sampling.py:253-285) run on CPU
+    on written .cnf / .wcnf texts, every torch draw recorded.  torch_scatter is not installed: its ``scatter(src, index,
+    reduce="max", dim=1)`` is stood in for by torch.scatter_reduce(..., "amax", include_self=False) on a zero tensor of
+    max(index) + 1 columns -- the fixture's ``source`` entry says so."""
+    import tempfile
+    smp = _load_upstream_mcpg("sampling")
+    dl = _load_upstream_mcpg("dataloader")
+
+    def scatter(src, index, reduce="max", dim=1):
+        assert reduce == "max" and dim == 1
+        n = int(index.max()) + 1 if index.numel() else 0
+        out = src.new_zeros((src.shape[0], n))
+        return out if n == 0 else out.scatter_reduce(1, index.long().unsqueeze(0).expand_as(src), src, "amax", include_self=False)
+
+    smp.scatter = scatter
+    cpu = th.device("cpu")
+    out, names = {}, []
+    for name, (ext, text, M, R, num_ls, change_times) in maxsat_fixture_texts().items():
+        with tempfile.NamedTemporaryFile("w", suffix=ext, delete=False) as f:
+            f.write(text)
+        th.manual_seed(5000 + len(names))
+        data, nvar = dl.maxsat_dataloader(f.name, device=cpu)
+        os.unlink(f.name)
+        C = M * R
+        g = th.Generator().manual_seed(88)
+        probs = th.rand(nvar, generator=g) * 0.6 + 0.2
+        start = th.randint(0, 2, (nvar, C), generator=g).float()
+        with Recorder("rand", "randint") as rec:
+            max_res, best, raw, value = smp.mcpg_sampling_maxsat(data, start.clone(), probs, num_ls, change_times, M, device=cpu)
+        T = len(rec.log["randint"])
+        assert len(rec.log["rand"]) == T + num_ls * nvar
+        t = name
+        names.append(name)
+        out[f"{t}/text"], out[f"{t}/ext"] = np.array(text), np.array(ext)
+        out[f"{t}/params"] = np.array([M, R, num_ls, change_times], dtype=np.int64)
+        out[f"{t}/order"] = data.ndata[3].numpy().copy()
+        out[f"{t}/degree"] = data.ndata[4].numpy().copy()
+        out[f"{t}/variable_index"] = np.asarray(data.pdata[2], dtype=np.int64)
+        out[f"{t}/clause_index"] = data.pdata[3].numpy().astype(np.int64)
+        out[f"{t}/neg_index"] = data.pdata[4].numpy().astype(np.int64)
+        out[f"{t}/extra"] = np.asarray(data.pdata[5:], dtype=np.int64)
+        out[f"{t}/nvi_len"] = np.array([len(v) for v in data.ndata[0]], dtype=np.int64)
+        out[f"{t}/nvi"] = th.cat([v.long() for v in data.ndata[0]]).numpy().astype(np.int32)
+        out[f"{t}/nci"] = th.cat([v.long() for v in data.ndata[1]]).numpy().astype(np.int32)
+        out[f"{t}/nneg"] = th.cat([v.long() for v in data.ndata[2]]).numpy().astype(np.int32)
+        out[f"{t}/probs"], out[f"{t}/start"] = probs.numpy().copy(), u8(start)
+        out[f"{t}/index"] = (th.stack(rec.log["randint"]) if T else th.zeros((0, C), dtype=th.int64)).numpy().astype(np.int16)
+        out[f"{t}/u"] = (th.stack(rec.log["rand"][:T]) if T else th.zeros((0, C))).numpy().copy()
+        out[f"{t}/uniforms"] = th.stack(rec.log["rand"][T:]).reshape(num_ls, nvar, C).numpy().copy()
+        out[f"{t}/max_res"], out[f"{t}/best"] = max_res.numpy().copy(), u8(best)
+        out[f"{t}/raw"], out[f"{t}/value"] = u8(raw), value.numpy().copy()
+    out["names"] = np.array(names)
+    out["source"] = np.array("recorded from the reference's own maxsat_dataloader / mcpg_sampling_maxsat on CPU, with a stand-in for "
+                             "torch_scatter.scatter built on torch.scatter_reduce(amax, include_self=False)")
+    save("maxsat", **out)
+
+
+ALL = {"graph_forms": gen_graph_forms, "maxsat": gen_maxsat, "mcpg_weighted": gen_mcpg_weighted, "isco_steps": gen_isco_steps, "isco_mis": gen_isco_mis, "spinsystem_cpu": gen_spinsystem_cpu, "spinsystem": gen_spinsystem, "spinsystem_perenv": gen_spinsystem_perenv, "qubo": gen_qubo, "qubo_asym": gen_qubo_asym, "isco_maxcut": gen_isco_maxcut, "maxcut": gen_maxcut, "sweep": gen_sweep, "lsclass": gen_local_search_class, "ppo": gen_ppo,
        "select": gen_select, "mcpg": gen_mcpg, "tsp": gen_tsp, "tsp_2opt": gen_tsp_2opt, "encoder": gen_encoder,
        "wgain": gen_weighted_gain, "mcpg_glue": gen_mcpg_glue, "evaluator": gen_evaluator, "spinsystem_options": gen_spinsystem_options,
        "api_surface": gen_api_surface, "mcpg_data": gen_mcpg_data,

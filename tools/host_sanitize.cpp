@@ -277,6 +277,54 @@ static void run_planners(std::mt19937_64& rng) {
               "TSP form N %lld K %d err %d lds %zu block %d waves %d", (long long)tn, tk, p.err, p.lds, p.block, p.waves);
 }
 
+// the MaxSAT level schedule (rls_maxsat_visit_levels) over random formulas: k-SAT with repeated variables, long clauses, empty
+// clauses, a hub variable, weighted or not, a random visiting order -- sized, then filled into buffers of exactly that size; every
+// entry points inside the tile, every variable sits in exactly one lane, a buffer one word short is refused
+static void run_maxsat(std::mt19937_64& rng, int it) {
+    const int nvar = 1 + (int)(rng() % (it % 7 == 0 ? 3000 : 90)), M = (int)(rng() % (5 * (uint64_t)nvar + 2));
+    const bool weighted = rng() % 3 == 0;
+    std::vector<int32_t> cp{0}, lit, w, order((size_t)nvar);
+    for (int c = 0; c < M; ++c) {
+        int k = (int)(rng() % 7);
+        if (rng() % 50 == 0) k = 40 + (int)(rng() % 30);
+        for (int j = 0; j < k; ++j) {
+            const int v = (j == 0 && it % 5 == 0) ? 0 : (int)(rng() % (uint64_t)nvar);
+            lit.push_back((v + 1) * ((rng() & 1) ? 1 : -1));
+        }
+        cp.push_back((int32_t)lit.size());
+        w.push_back(1 + (int32_t)(rng() % 20));
+    }
+    for (int i = 0; i < nvar; ++i) order[(size_t)i] = i;
+    for (int i = nvar - 1; i > 0; --i) std::swap(order[(size_t)i], order[(size_t)(rng() % (uint64_t)(i + 1))]);
+    const int32_t* wp = weighted ? w.data() : nullptr;
+    int64_t ng = 0, tot = 0, ng2 = 0, tot2 = 0;
+    CHECK(rls_maxsat_visit_levels(cp.data(), lit.data(), wp, nvar, M, order.data(), nullptr, 0, nullptr, 0, &ng, &tot) == RLS_OK, "maxsat sizing: %s",
+          rls_last_error_string());
+    std::vector<int32_t> lvp((size_t)ng + 1), lvd((size_t)tot);
+    CHECK(rls_maxsat_visit_levels(cp.data(), lit.data(), wp, nvar, M, order.data(), lvp.data(), (int64_t)lvp.size(), lvd.data(), (int64_t)lvd.size(),
+                                  &ng2, &tot2) == RLS_OK && ng2 == ng && tot2 == tot, "maxsat fill: %s", rls_last_error_string());
+    std::vector<int> seen((size_t)nvar, 0);
+    const int64_t B = weighted ? 512 : 256;
+    for (int64_t g = 0; g < ng; ++g) {
+        const int64_t p0 = (int64_t)(lvp[(size_t)g] & 0xFFFFFF) * 64, p1 = (int64_t)(lvp[(size_t)g + 1] & 0xFFFFFF) * 64;
+        CHECK(p0 + 128 <= p1 && p1 + 512 <= tot && (p1 - p0 - 128) % B == 0, "maxsat record %lld", (long long)g);
+        for (int l = 0; l < 64; ++l)
+            if (lvd[(size_t)(p0 + 2 * l)] < nvar) ++seen[(size_t)lvd[(size_t)(p0 + 2 * l)]];
+        for (int64_t b = 0; p0 + 128 + b * B < p1; ++b)
+            for (int e = 0; e < 256; ++e)
+                CHECK((((uint32_t)lvd[(size_t)(p0 + 128 + b * B + e)] & 0x3FFF8u) >> 3) <= (uint32_t)nvar, "maxsat entry past the tile");
+    }
+    for (int v = 0; v < nvar; ++v) CHECK(seen[(size_t)v] == 1, "maxsat: variable %d scheduled %d times", v, seen[(size_t)v]);
+    std::vector<int32_t> small((size_t)tot - 1);
+    CHECK(rls_maxsat_visit_levels(cp.data(), lit.data(), wp, nvar, M, order.data(), lvp.data(), (int64_t)lvp.size(), small.data(),
+                                  (int64_t)small.size(), &ng2, &tot2) == RLS_EINVAL, "maxsat: a short buffer was accepted");
+    if (!lit.empty()) {
+        lit[(size_t)(rng() % lit.size())] = (rng() & 1) ? 0 : nvar + 1;
+        CHECK(rls_maxsat_visit_levels(cp.data(), lit.data(), wp, nvar, M, order.data(), nullptr, 0, nullptr, 0, &ng2, &tot2) == RLS_EINVAL,
+              "maxsat: a bad literal was accepted");
+    }
+}
+
 int main(int argc, char** argv) {
     const int iters = argc > 1 ? std::atoi(argv[1]) : 200;
     std::mt19937_64 rng(argc > 2 ? (uint64_t)std::atoll(argv[2]) : 20261003ull);
@@ -291,6 +339,7 @@ int main(int argc, char** argv) {
         run_builders(g, rng);
         run_oracle(g, rng);
         for (int k = 0; k < 50; ++k) run_planners(rng);
+        run_maxsat(rng, it);
     }
     std::printf("host_sanitize: %d random graphs through the host builders and the C oracle, clean\n", iters);
     return 0;
