@@ -95,8 +95,11 @@ def accept(new, old, u):
     return new.astype(F) > ((old.astype(F) + u.astype(F)).astype(F) - F(0.5)).astype(F)
 
 
-def sweep(inst, s, order, num_ls, uniforms):
-    """s float32 [C, nvar] of -1 | +1, in place; uniforms [num_ls, nvar (visiting position), C]."""
+def visit(inst, s, order, num_ls, decide):
+    """The node-sequential sweep with the accept rule left to the caller.  s float32 [C, nvar] of -1 | +1, in place.  For every
+    pass and visiting position: old = the listed sum of variable i, new = the same with s_i negated, and
+    decide(cnt, pos, i, old, new) -> bool [C] says in which chains the flip is kept (s[:, i] holds the FLIPPED value when it is
+    called).  sweep, coin_rule_agrees and the tests that follow the kernel through its ties are this one loop."""
     for cnt in range(num_ls):
         for pos in range(inst.nvar):
             i = int(order[pos])
@@ -105,9 +108,14 @@ def sweep(inst, s, order, num_ls, uniforms):
             old = _segment_max_sum(s[:, idx] * ng, seg)
             s[:, i] = -s[:, i]
             new = _segment_max_sum(s[:, idx] * ng, seg)
-            keep = accept(new, old, uniforms[cnt, pos])
+            keep = decide(cnt, pos, i, old, new)
             s[:, i] = np.where(keep, s[:, i], -s[:, i])
     return s
+
+
+def sweep(inst, s, order, num_ls, uniforms):
+    """s float32 [C, nvar] of -1 | +1, in place; uniforms [num_ls, nvar (visiting position), C]."""
+    return visit(inst, s, order, num_ls, lambda cnt, pos, i, old, new: accept(new, old, uniforms[cnt, pos]))
 
 
 def score(inst, s):
@@ -138,21 +146,15 @@ def sampling(inst, order, start, probs, num_ls, change_times, M, index, u, unifo
 def coin_rule_agrees(inst, s, order, num_ls, uniforms):
     """True when, on this run, the float32 rule equals  d > 0 or (d == 0 and u < 1/2)  at every decision (what the
     kernel computes from coins): replays the sweep with both."""
-    s = s.copy()
-    for cnt in range(num_ls):
-        for pos in range(inst.nvar):
-            i = int(order[pos])
-            idx, seg = np.asarray(inst.nvi[i], dtype=np.int64), np.asarray(inst.nci[i], dtype=np.int64)
-            ng = np.asarray(inst.nneg[i], dtype=F)
-            old = _segment_max_sum(s[:, idx] * ng, seg)
-            s[:, i] = -s[:, i]
-            new = _segment_max_sum(s[:, idx] * ng, seg)
-            keep = accept(new, old, uniforms[cnt, pos])
-            d = new.astype(np.float64) - old.astype(np.float64)
-            if not np.array_equal(keep, (d > 0) | ((d == 0) & (uniforms[cnt, pos] < F(0.5)))):
-                return False
-            s[:, i] = np.where(keep, s[:, i], -s[:, i])
-    return True
+    agree = [True]
+
+    def decide(cnt, pos, i, old, new):
+        keep = accept(new, old, uniforms[cnt, pos])
+        d = new.astype(np.float64) - old.astype(np.float64)
+        agree[0] = agree[0] and np.array_equal(keep, (d > 0) | ((d == 0) & (uniforms[cnt, pos] < F(0.5))))
+        return keep
+    visit(inst, s.copy(), order, num_ls, decide)
+    return agree[0]
 
 
 def prepare_uniforms(u):

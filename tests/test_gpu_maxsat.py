@@ -45,19 +45,27 @@ def build(nvar, clauses, weights=None, top=None, nclause=None, order=None):
     return data, orc.Instance(nvar, clauses, weights, top, nclause), order
 
 
-def check_kernel(data, inst, order, C, num_ls, seed, c_in=None, packed_out=True):
-    """Sweep + score on random chains with recorded uniforms: chains and expected equal the oracle's."""
+def recorded_draws(rng, shape):
+    """Uniforms as a recorded run has them, prepared (maxsat_oracle.prepare_uniforms): what every test of this file draws."""
+    return orc.prepare_uniforms(rng.rand(max(shape[0], 1), *shape[1:]).astype(np.float32)[:shape[0]])
+
+
+def check_kernel(data, inst, order, C, num_ls, seed, c_in=None, packed_out=True, draw=recorded_draws, start=None, in_place=False):
+    """Sweep + score on random chains (or on `start` 0|1 [nvar, c_in]) with the uniforms of `draw(rng, shape)`: chains and
+    expected equal the oracle's.  Chain c of a broadcast start (c_in < C) starts from chain c % c_in."""
     rng = np.random.RandomState(seed)
     c_in = C if c_in is None else c_in
-    start = (rng.rand(inst.nvar, c_in) < 0.5).astype(np.float32)
-    uni = orc.prepare_uniforms(rng.rand(max(num_ls, 1), inst.nvar, C).astype(np.float32)[:num_ls])
-    s = (np.tile(start, (1, C // c_in)).T * 2 - 1).astype(np.float32)
+    start = (rng.rand(inst.nvar, c_in) < 0.5).astype(np.float32) if start is None else np.asarray(start, dtype=np.float32)
+    assert start.shape == (inst.nvar, c_in)
+    uni = draw(rng, (num_ls, inst.nvar, C))
+    s = (start[:, np.arange(C) % c_in].T * 2 - 1).astype(np.float32)
     assert orc.coin_rule_agrees(inst, s, order, num_ls, uni)
     orc.sweep(inst, s, order, num_ls, uni)
     coins = ms().maxsat_tie_coins_from_uniforms(torch.from_numpy(uni).to(dev())) if num_ls else None
     xin = packed().pack(torch.from_numpy(start).to(dev()))
-    out = packed().empty(inst.nvar, C, dev()) if packed_out else None
+    out = (xin if in_place else packed().empty(inst.nvar, C, dev())) if packed_out else None
     xs, expected = data.local_search(xin, num_ls, coins=coins, out=out, num_chains=C)
+    assert not in_place or xs is xin
     got = (xs.unpack() if packed_out else xs).cpu().numpy()
     assert np.array_equal(got, (s.T + 1) / 2)
     assert np.array_equal(expected.cpu().numpy(), -orc.score(inst, s))
