@@ -761,6 +761,37 @@ int rls_maxsat_local_search(const void* xs_in, int64_t C_in, void* xs_out, int o
                             const uint64_t* coins, uint64_t seed, const int32_t* clause_ptr, const int32_t* lit,
                             const int32_t* weight, int64_t M, float* expected, const rls_chain_ids* chain_ids, void* stream);
 
+/* ------------------------------------------------------------ Cheeger cuts */
+
+/* [host] 1 when the Cheeger sampler covers a graph of N nodes and E stored edges whose weights sum to weight_abs_sum in absolute
+ * value, else 0 (additive: the ABI stays v12).  The two limits:
+ *   RLS_CHEEGER_MAX_NODES  the 64-chain tile uint64 [N] is all the kernel keeps in LDS: N <= 160 KB / 8 = 20 480 (*max_N, may be NULL);
+ *   RLS_CHEEGER_EXACT      weight_abs_sum + 2 E < 2^24 and N < 2^24: cut, size and every intermediate of the rule below are then
+ *                          integers or half-integers that float32 holds exactly, as they are in the reference. */
+#define RLS_CHEEGER_MAX_NODES 20480
+#define RLS_CHEEGER_EXACT (1 << 24)
+int rls_cheeger_local_search_supported(int64_t N, int64_t E, int64_t weight_abs_sum, int64_t* max_N);
+
+/* The sweep and the score of mcpg_sampling_rcheegercut / mcpg_sampling_ncheegercut  methods/MCPG/sampling.py:181-250 in ONE
+ * kernel: lane = chain, one wave per 64-chain tile, the tile uint64 [N] in LDS, cut / size / h in registers.  Per chain, float32:
+ *     s_v = 2 x_v - 1;  cut = (edge_weight_sum - sum_e s_u s_v) / 2   (the edge sum is UNWEIGHTED, over g's stored edges: :190-191)
+ *     size = sum_v x_v;  h = cut / min(size, N - size)  (normalized = 0, :193)   |   cut * (1 / size + 1 / (N - size))  (1, :229)
+ *     num_ls times, for every node in visiting order:
+ *         c = sum_{j in neighbours[node]} x_j              unweighted, with multiplicity (a self-loop lists the node twice)
+ *         ncut = cut - s_node (weighted_degree[node] - 2 c);  nsize = size - s_node;  nh = the same formula on (ncut, nsize)
+ *         keep = (h < nh) or (min(nsize, N - nsize) < 1e-7);  if not keep: flip x_node and cut, size, h = ncut, nsize, nh
+ * The rule draws nothing and is sequential per chain: every decision reads cut, size and h as the flips before it left them.
+ * Divisions are IEEE (1 / 0 = inf, 0 / 0 = NaN, 0 * inf = NaN); NaN exists only before the first visit (num_ls = 0).
+ * xs_in: bit-packed chains holding 0|1, C_in as in rls_mcpg_metro_rounds; xs_out: bit-packed (out_spin_bytes = 0; may alias
+ * xs_in when C_in == C) or float32 node-major [N, C] (4).  visit_stream int32 [3 N + nnz] on the device, one record per visiting
+ * position:  node, degree, weighted degree, then the `degree` neighbours (node = index of its uint64 word in the tile); a record
+ * that points past N or past stream_len ends the pass.  num_ls = 0 only scores.  Outputs f32 [C]: h, and cut / size after the
+ * last pass (either may be NULL).  RLS_EUNSUPPORTED outside rls_cheeger_local_search_supported (|edge_weight_sum| stands in for
+ * the absolute sum, which a caller checks on the host); RLS_EINVAL for a stream of another length. */
+int rls_cheeger_local_search(const rls_graph* g, const void* xs_in, int64_t C_in, void* xs_out, int out_spin_bytes, int64_t C,
+                             const int32_t* visit_stream, int64_t stream_len, int normalized, int64_t num_ls, float edge_weight_sum,
+                             float* h, float* cut, float* size, void* stream);
+
 /* --------------------------------------------------------------------- TSP */
 
 /* K12 ISCO_TSP.calculate_distance(sample)  envs/env_ISCO.py:346-350.

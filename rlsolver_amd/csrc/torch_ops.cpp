@@ -685,6 +685,34 @@ void maxsat_local_search(const Tensor& xs_in, int64_t C_in, Tensor xs_out, int64
                                (const int32_t*)p(weight), M, (float*)p(expected), cid.ptr(), cur_stream(xs_in)),
        "rls_maxsat_local_search");
 }
+void cheeger_local_search(int64_t g, const Tensor& xs_in, int64_t C_in, Tensor xs_out, int64_t C, const Tensor& visit_stream, int64_t normalized,
+                          int64_t num_ls, double edge_weight_sum, Tensor h, const OptTensor& cut, const OptTensor& size) {
+    const int64_t N = G(g)->num_nodes;
+    dev(xs_in, "xs_in", I64);
+    TORCH_CHECK(C >= 0 && C_in >= 0, "C and C_in must be >= 0");
+    chain_shape(xs_in, 0, N, C_in > 0 ? C_in : C, "xs_in");
+    const int osb = chain_bytes(xs_out, "xs_out");
+    TORCH_CHECK(osb == 0 || osb == 4, "xs_out must be float32 node-major or bit-packed");
+    chain_shape(xs_out, osb, N, C, "xs_out");
+    dev(visit_stream, "visit_stream", I32);
+    TORCH_CHECK(visit_stream.dim() == 1 && visit_stream.numel() == 3 * N + G(g)->nnz, "visit_stream must hold 3 N + nnz = ", 3 * N + G(g)->nnz,
+                " entries (one record per visiting position), got ", visit_stream.sizes());
+    TORCH_CHECK(normalized == 0 || normalized == 1, "normalized must be 0 (ratio) or 1 (normalised)");
+    TORCH_CHECK(num_ls >= 0, "num_ls must be >= 0");
+    dev(h, "h", F32);
+    count(h, "h", C);
+    optdev(cut, "cut", F32);
+    if (cut.has_value()) count(*cut, "cut", C);
+    optdev(size, "size", F32);
+    if (size.has_value()) count(*size, "size", C);
+    for (const Tensor* t : {(const Tensor*)&xs_out, &visit_stream, (const Tensor*)&h}) same_device(xs_in, *t, "every tensor");
+    if (cut.has_value()) same_device(xs_in, *cut, "cut");
+    if (size.has_value()) same_device(xs_in, *size, "size");
+    RLS_GUARD(xs_in);
+    ok(rls_cheeger_local_search(G(g), p(xs_in), C_in, p(xs_out), osb, C, (const int32_t*)p(visit_stream), visit_stream.numel(), (int)normalized, num_ls,
+                                (float)edge_weight_sum, (float*)p(h), (float*)p(cut), (float*)p(size), cur_stream(xs_in)),
+       "rls_cheeger_local_search");
+}
 void mcpg_pick_best(const Tensor& expected, const Tensor& xs, int64_t N, int64_t total_mcmc_num, int64_t repeat_times, int64_t num_edges,
                     Tensor best_index, Tensor vs_good, Tensor xs_good) {
     dev(expected, "expected", F32);
@@ -1047,6 +1075,8 @@ TORCH_LIBRARY(rlsolver_hip, m) {
           "int seed, int env_offset, Tensor(b!)? energy_out, Tensor(c!)? acc_out, Tensor(d!)? terms_out, Tensor(e!)? mask_out, Tensor(f!)? scratch=None) -> ()");
     m.def("maxsat_local_search(Tensor xs_in, int C_in, Tensor(a!) xs_out, int C, Tensor lv_ptr, Tensor lv_data, int num_ls, Tensor? coins, "
           "int seed, Tensor clause_ptr, Tensor lit, Tensor? weight, Tensor(b!) expected, int chain_offset=0, int chain_period=0, int chain_skip=0) -> ()");
+    m.def("cheeger_local_search(int graph, Tensor xs_in, int C_in, Tensor(a!) xs_out, int C, Tensor visit_stream, int normalized, int num_ls, "
+          "float edge_weight_sum, Tensor(b!) h, Tensor(c!)? cut=None, Tensor(d!)? size=None) -> ()");
     m.def("isco_mis_step(int graph, Tensor x, Tensor(a!) y_out, Tensor path_length, float temperature, float lam, Tensor? u_gumbel, Tensor? u_accept, "
           "int seed, int env_offset, Tensor(b!)? energy_out, Tensor(c!)? acc_out, Tensor(d!)? terms_out, Tensor(e!)? mask_out, Tensor(f!)? scratch=None) -> ()");
     m.def("isco_tsp_step(Tensor dist, Tensor nearest, float near_threshold, Tensor random, Tensor perm_in, Tensor(a!) perm_out, int path_length, "
@@ -1106,5 +1136,6 @@ TORCH_LIBRARY_IMPL(rlsolver_hip, CUDA, m) {   // "CUDA" is the HIP dispatch key 
     m.impl("isco_maxcut_step", &isco_maxcut_step);
     m.impl("isco_mis_step", &isco_mis_step);
     m.impl("maxsat_local_search", &maxsat_local_search);
+    m.impl("cheeger_local_search", &cheeger_local_search);
     m.impl("isco_tsp_step", &isco_tsp_step);
 }

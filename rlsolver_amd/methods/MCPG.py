@@ -192,6 +192,31 @@ def build_visit_stream(csr, order: np.ndarray, max_nodes: int = 32, max_entries:
     return (stream & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
 
 
+def build_cheeger_stream(csr, order: np.ndarray) -> np.ndarray:
+    """Flatten the visiting order for the Cheeger-cut sweep (format: include/rlsolver_hip.h: rls_cheeger_local_search): int32
+    [3 N + nnz], one record per visiting position -- node, degree, weighted degree, then the node's neighbour row of the
+    symmetric CSR (with multiplicity; a self-loop lists the node twice when the CSR keeps loops).  The sweep is sequential per
+    chain (every decision reads the cut and the side size all earlier flips left), so there is no level schedule: the records
+    simply follow the order."""
+    n = csr.num_nodes
+    order = np.asarray(order, dtype=np.int64)
+    if order.shape != (n,) or not np.array_equal(np.sort(order), np.arange(n)):
+        raise ValueError("order must be a permutation of the nodes")
+    rowptr = csr.rowptr.astype(np.int64)
+    deg_o = np.diff(rowptr)[order]
+    nnz = int(deg_o.sum())
+    cum = np.concatenate([[0], np.cumsum(deg_o)])
+    idx = np.repeat(rowptr[order] - cum[:-1], deg_o) + np.arange(nnz)            # rows gathered in visiting order
+    wdeg = np.bincount(np.repeat(np.arange(n), deg_o), weights=csr.wgt[idx].astype(np.float64), minlength=n).astype(np.int64)
+    if nnz and np.abs(wdeg).max() >= 2 ** 31:
+        raise ValueError("a weighted degree does not fit int32")
+    rec = cum[:-1] + 3 * np.arange(n)
+    stream = np.empty(3 * n + nnz, dtype=np.int64)
+    stream[rec], stream[rec + 1], stream[rec + 2] = order, deg_o, wdeg
+    stream[np.repeat(rec + 3 - cum[:-1], deg_o) + np.arange(nnz)] = csr.col[idx]
+    return stream.astype(np.int32)
+
+
 ACCEPT_ROWS = 64      # rows the kernels spread their per-round accept counts over (one row = thousands of atomics per address)
 
 
@@ -469,6 +494,9 @@ class MCPGRound(Sharded):
             raise NotImplementedError("this problem family runs on the bit-packed walk only (N <= ~16 000)")
         if self._nodemajor and self.sharded:
             raise NotImplementedError("a sharded MCPGRound needs the bit-packed walk (N <= ~16 000)")
+        if self.sharded and getattr(data, "fractional_values", False):
+            raise NotImplementedError("a sharded MCPGRound exchanges its incumbents as integer MAXLOC keys; this family's values (Cheeger "
+                                      "cuts: a cut divided by a side size) are neither integers nor half-integers: run it unsharded")
         if self.sharded and self.now_max_res.numel():
             # the incumbents travel between ranks as a packed MAXLOC key of DOUBLED integers (dist.global_best): cut values of
             # this build's integer-weighted graphs are integers or half-integers.  Anything else would trip a device-side assert

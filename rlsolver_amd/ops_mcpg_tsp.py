@@ -221,6 +221,35 @@ def mcpg_maxsat_local_search(xs_in: PackedChains, lv_ptr: TEN, lv_data: TEN, cla
     return xs_out, expected
 
 
+def mcpg_cheeger_local_search(g: DeviceGraph, xs_in: PackedChains, visit_stream: TEN, normalized: bool, num_ls: int, edge_weight_sum: float,
+                              out=None, num_chains: Optional[int] = None, want_cut_size: bool = True):
+    """The sweep and the score of the two Cheeger-cut samplers (include/rlsolver_hip.h: rls_cheeger_local_search).  ``xs_in``:
+    PackedChains over the nodes (may hold fewer chains than ``num_chains``, a multiple of 64: broadcast); ``visit_stream`` int32
+    [3 N + nnz]: the records of methods/MCPG_cheeger.py: build_cheeger_stream in visiting order; ``normalized``: the normalised cut
+    (ncheegercut) instead of the ratio cut.  ``out``: a PackedChains to write (may be xs_in itself) or None = node-major f32.
+    ``num_ls = 0`` only scores (the one case where h can hold NaN: an empty side, 0 / 0).
+    Returns (xs_out, h f32 [C], cut f32 [C], size f32 [C]); cut and size are None with ``want_cut_size=False``."""
+    if not isinstance(xs_in, PackedChains):
+        raise TypeError("xs_in must be a PackedChains")
+    dev, N = xs_in.device, xs_in.num_nodes
+    if dev != g.device or N != g.num_nodes:
+        raise ValueError(f"xs_in must hold {g.num_nodes} nodes on {g.device}")
+    Cc = xs_in.num_chains if num_chains is None else num_chains
+    _check(visit_stream, "visit_stream", (torch.int32,), dev, (3 * N + g.nnz,))
+    if out is None:
+        xs_out = ot = torch.empty((N, Cc), dtype=torch.float32, device=dev)
+    else:
+        if not isinstance(out, PackedChains) or out.num_chains != Cc or out.num_nodes != N or out.device != dev:
+            raise ValueError("out must be a PackedChains of num_chains chains")
+        xs_out, ot = out, out.words
+    h = torch.empty(Cc, dtype=torch.float32, device=dev)
+    cut = torch.empty(Cc, dtype=torch.float32, device=dev) if want_cut_size else None
+    size = torch.empty(Cc, dtype=torch.float32, device=dev) if want_cut_size else None
+    _t.cheeger_local_search(g.handle, xs_in.words, xs_in.num_chains, ot, Cc, visit_stream, int(bool(normalized)), int(num_ls),
+                            float(edge_weight_sum), h, cut, size)
+    return xs_out, h, cut, size
+
+
 def mcpg_pick_best(expected: TEN, xs, total_mcmc_num: int, repeat_times: int, num_edges: int):
     """K8 second half.  Returns (best_index int64 [M], vs_good f32 [M], xs_good: f32 [N, M] or PackedChains of M chains)."""
     st, sb, N, Cc = _chains(xs, "xs")

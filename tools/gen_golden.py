@@ -1783,7 +1783,69 @@ def gen_maxsat():
     save("maxsat", **out)
 
 
-ALL = {"graph_forms": gen_graph_forms, "maxsat": gen_maxsat, "mcpg_weighted": gen_mcpg_weighted, "isco_steps": gen_isco_steps, "isco_mis": gen_isco_mis, "spinsystem_cpu": gen_spinsystem_cpu, "spinsystem": gen_spinsystem, "spinsystem_perenv": gen_spinsystem_perenv, "qubo": gen_qubo, "qubo_asym": gen_qubo_asym, "isco_maxcut": gen_isco_maxcut, "maxcut": gen_maxcut, "sweep": gen_sweep, "lsclass": gen_local_search_class, "ppo": gen_ppo,
+CHEEGER_GRAPHS = ("BA_5_ID0", "PL_20_ID0", "BA_100_ID0", "ER_100_ID0", "gset_14_stub")
+CHEEGER_CONFIGS = ((5, 3), (64, 2))          # (total_mcmc_num, repeat_times)
+
+
+def gen_cheeger():
+    """mcpg_sampling_rcheegercut / mcpg_sampling_ncheegercut (rlsolver/methods/MCPG/sampling.py:181-250) and sample_initializer
+    (:7-20) run on CPU on graphs loaded by the package's own maxcut_dataloader (dataloader.py:53-103); the walk's draws recorded.
+    Per (graph, M x R, start kind) one walk -- the same seed before every call, so both samplers and both num_ls see the same
+    draws and the same raw samples -- and per (sampler, num_ls) the three other returns.  Chains are stored as bits (np.packbits
+    along the node axis)."""
+    smp = _load_upstream_mcpg("sampling")
+    dl = _load_upstream_mcpg("dataloader")
+    cpu = th.device("cpu")
+    bits = lambda t: np.packbits(u8(t), axis=0)      # noqa: E731
+    out, names = {}, []
+    for gi, gname in enumerate(CHEEGER_GRAPHS):
+        data, n = dl.maxcut_dataloader(os.path.join(DATA, GRAPHS[gname]), device=cpu)
+        out[f"{gname}/edges"] = data.edge_index.numpy().astype(np.int32)
+        out[f"{gname}/weights"] = data.edge_attr[:, 0].numpy().astype(np.int32)
+        out[f"{gname}/num_nodes"] = np.int64(n)
+        out[f"{gname}/sorted_degree_nodes"] = data.sorted_degree_nodes.numpy().astype(np.int32)
+        for ci, (M, R) in enumerate(CHEEGER_CONFIGS):
+            cfg = types.SimpleNamespace(total_mcmc_num=M, repeat_times=R)
+            C = M * R
+            g = th.Generator().manual_seed(4100 + 10 * gi + ci)
+            probs = th.rand(n, generator=g) * 0.6 + 0.2
+            for kind in ("onehot", "bernoulli"):
+                th.manual_seed(4200 + 10 * gi + ci)
+                if kind == "onehot":
+                    start = smp.sample_initializer(smp.Problem.rcheegercut, probs, cfg, device=cpu, data=data)
+                    change_times = 0
+                else:
+                    start = smp.sample_initializer(smp.Problem.maxcut, probs, cfg, device=cpu, data=data)
+                    change_times = n // 10
+                start = start.contiguous()
+                key = f"{gname}/{M}x{R}/{kind}"
+                walk = None
+                for fn_name in ("rcheegercut", "ncheegercut"):
+                    fn = getattr(smp, "mcpg_sampling_" + fn_name)
+                    for num_ls in (1, 2):
+                        th.manual_seed(4300 + 10 * gi + ci)
+                        with Recorder("rand", "randint") as rec:
+                            neg_h, best, raw, value = fn(data, start.clone(), probs, num_ls, change_times, M, device=cpu)
+                        T = len(rec.log["randint"])
+                        assert len(rec.log["rand"]) == T
+                        index = (th.stack(rec.log["randint"]) if T else th.zeros((0, C), dtype=th.int64)).numpy().astype(np.int16)
+                        u = (th.stack(rec.log["rand"]) if T else th.zeros((0, C))).numpy().copy()
+                        if walk is None:
+                            walk = (index, u, u8(raw))
+                            out[f"{key}/probs"], out[f"{key}/start"] = probs.numpy().copy(), bits(start)
+                            out[f"{key}/change_times"] = np.int64(change_times)
+                            out[f"{key}/index"], out[f"{key}/u"], out[f"{key}/raw"] = index, u, bits(raw)
+                        assert np.array_equal(walk[0], index) and np.array_equal(walk[1], u) and np.array_equal(walk[2], u8(raw))
+                        t = f"{key}/{fn_name}/ls{num_ls}"
+                        names.append(t)
+                        out[f"{t}/neg_h"], out[f"{t}/best"], out[f"{t}/value"] = neg_h.numpy().copy(), bits(best), value.numpy().copy()
+    out["names"] = np.array(names)
+    out["source"] = np.array("recorded from the reference's own maxcut_dataloader, sample_initializer, mcpg_sampling_rcheegercut and "
+                             "mcpg_sampling_ncheegercut on CPU; chains as np.packbits(axis=0) of the [N, C] 0|1 arrays")
+    save("cheeger", **out)
+
+
+ALL = {"graph_forms": gen_graph_forms, "cheeger": gen_cheeger, "maxsat": gen_maxsat, "mcpg_weighted": gen_mcpg_weighted, "isco_steps": gen_isco_steps, "isco_mis": gen_isco_mis, "spinsystem_cpu": gen_spinsystem_cpu, "spinsystem": gen_spinsystem, "spinsystem_perenv": gen_spinsystem_perenv, "qubo": gen_qubo, "qubo_asym": gen_qubo_asym, "isco_maxcut": gen_isco_maxcut, "maxcut": gen_maxcut, "sweep": gen_sweep, "lsclass": gen_local_search_class, "ppo": gen_ppo,
        "select": gen_select, "mcpg": gen_mcpg, "tsp": gen_tsp, "tsp_2opt": gen_tsp_2opt, "encoder": gen_encoder,
        "wgain": gen_weighted_gain, "mcpg_glue": gen_mcpg_glue, "evaluator": gen_evaluator, "spinsystem_options": gen_spinsystem_options,
        "api_surface": gen_api_surface, "mcpg_data": gen_mcpg_data,
