@@ -1028,10 +1028,12 @@ __global__ __launch_bounds__(1024) void k_mcpg_merge_minmax(float* __restrict__ 
     __shared__ int64_t s_hii[16], s_loi[16];
     float hi = -INFINITY, lo = INFINITY;
     int64_t hii = INT64_MAX, loi = INT64_MAX;
+    // A value becomes the running best (worst) if it compares greater (less), or if none has been taken yet and it is not NaN:
+    // an index of INT64_MAX means "nothing taken", and -inf (+inf) incumbents are taken like any other.  NaN is never taken.
     for (int64_t m = threadIdx.x; m < M; m += blockDim.x) {
         const float v = now_max_res[m];
-        if (v > hi) { hi = v; hii = m; }
-        if (v < lo) { lo = v; loi = m; }
+        if (v > hi || (hii == INT64_MAX && v == v)) { hi = v; hii = m; }
+        if (v < lo || (loi == INT64_MAX && v == v)) { lo = v; loi = m; }
     }
 #pragma unroll
     for (int s = 32; s >= 1; s >>= 1) {
@@ -1047,6 +1049,7 @@ __global__ __launch_bounds__(1024) void k_mcpg_merge_minmax(float* __restrict__ 
         if (s_hi[k] > hi || (s_hi[k] == hi && s_hii[k] < hii)) { hi = s_hi[k]; hii = s_hii[k]; }
         if (s_lo[k] < lo || (s_lo[k] == lo && s_loi[k] < loi)) { lo = s_lo[k]; loi = s_loi[k]; }
     }
+    if (hii == INT64_MAX) { hi = lo = now_max_res[0]; hii = loi = 0; }          // every incumbent is NaN: argmax = argmin = 0, like torch's
     if (!replace_worst) {   // a shard of the kept chains: the caller replaces the GLOBAL worst by the GLOBAL best itself
         if (threadIdx.x == 0) {
             best_value[0] = hi; best_value[1] = lo;

@@ -23,7 +23,7 @@ __global__ __launch_bounds__(kTrackThreads) void k_best_update(const uint8_t* __
     int64_t bi = INT64_MAX;
     for (int64_t b = threadIdx.x; b < B; b += kTrackThreads) {           // first extremum, like torch.argmax / argmin
         const double v = sign * (double)vs[b];
-        if (v > bv) { bv = v; bi = b; }
+        if (v > bv || (bi == INT64_MAX && v == v)) { bv = v; bi = b; }   // INT64_MAX: nothing taken yet -- the first non-NaN value is, -inf included
     }
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) {
@@ -36,6 +36,7 @@ __global__ __launch_bounds__(kTrackThreads) void k_best_update(const uint8_t* __
     if (threadIdx.x == 0) {
         for (int w = 1; w < kTrackThreads / 64; ++w)
             if (s_val[w] > bv || (s_val[w] == bv && s_idx[w] < bi)) { bv = s_val[w]; bi = s_idx[w]; }
+        if (bi == INT64_MAX) { bv = sign * (double)vs[0]; bi = 0; }      // every value is NaN: row 0, like torch.argmax / argmin
         const double good = sign * bv;
         const bool take = force || (if_maximize ? good > best_v[0] : good < best_v[0]);   // strict, util_evaluator.py:103
         if (take) best_v[0] = good;
@@ -105,7 +106,7 @@ __global__ __launch_bounds__(kTrackThreads) void k_best_key(const V* __restrict_
         const bool ok = r == scaled && fabs(r) < (double)limit;
         const int64_t best = ok ? (int64_t)r : 0;
         key[0] = (int64_t)((uint64_t)best << rank_bits) | low_code;      // (arithmetic meaning: best * 2^rank_bits + low_code)
-        if (index) index[0] = bi;
+        if (index) index[0] = bi == INT64_MAX ? 0 : bi;                  // nothing compared greater than -inf (all -inf / NaN; flagged below): a row that exists
         if (!ok) atomicOr(flag, 1);
     }
 }
