@@ -792,6 +792,49 @@ int rls_cheeger_local_search(const rls_graph* g, const void* xs_in, int64_t C_in
                              const int32_t* visit_stream, int64_t stream_len, int normalized, int64_t num_ls, float edge_weight_sum,
                              float* h, float* cut, float* size, void* stream);
 
+/* ------------------------------------------------------- edge-flip MaxCut */
+
+/* [host] 1 when the edge-flip MaxCut sampler covers a graph of N nodes and E stored edges whose largest sum of |weights| at a node
+ * is max_abs_degree, whose |weights| sum to weight_abs_sum and whose visit stream holds stream_len words, else 0 (additive: the ABI
+ * stays v12).  The limits:
+ *   RLS_MAXCUT_EDGE_MAX_NODES  the 64-chain tile uint64 [N] and a bitmap of the written nodes (N bits) are what the kernel keeps in
+ *                              LDS: 8 N (rounded up to 16) + 4 ceil(N / 32) <= 160 KB, N <= 20 164 (*max_N, may be NULL);
+ *   RLS_MAXCUT_EDGE_EXACT      3 max_abs_degree < 2^24 (a neighbour sum t is a half-integer of at most 1.5 max_abs_degree: the
+ *                              kernel counts 2 t in integers, and float32 holds it exactly, as it does in the reference) and
+ *                              weight_abs_sum < 2^24 (the score is an integer float32 holds exactly);
+ *   stream_len < 2^31. */
+#define RLS_MAXCUT_EDGE_MAX_NODES 20164
+#define RLS_MAXCUT_EDGE_EXACT (1 << 24)
+int rls_maxcut_edge_local_search_supported(int64_t N, int64_t E, int64_t max_abs_degree, int64_t weight_abs_sum, int64_t stream_len,
+                                           int64_t* max_N);
+
+/* Everything after the walk of mcpg_sampling_maxcut_edge  methods/MCPG/sampling.py:141-172 in ONE kernel (the loader's per-edge
+ * rows and `add` table, methods/MCPG/dataloader.py:87-101, :125-153, arrive as the visit stream): lane = chain, one wave per
+ * 64-chain tile, the tile uint64 [N] in LDS.  Per chain:
+ *     gauge_node >= 0: x ^= x[gauge_node] (:142-144); a node then holds v = 2 x - 0.5 until its first write, x afterwards (:145)
+ *     num_ls times, for every position i of the stream (edge e = sorted_degree_edges[i], r = eu[e], c = ev[e]):
+ *         t_r = sum_k w_k v[nbr_k] over row(r) less its first entry c, t_c over row(c) less its first entry r   (:161-162)
+ *         a = (t_r + u0 * 0.1f) + add0;  b = (t_c + u1 * 0.1f) + add1;  z = ((a + b) + u2 * 0.1f) - add2     (float32, :163-165)
+ *         k = first maximum of (z, a, b, 0);  x[r] = k >> 1, then x[c] = k & 1                                  (:166-168)
+ *     expected = sum_e edge_weights[e] (2 x_u - 1)(2 x_v - 1) over g's stored edges                             (:172)
+ * The sweep is sequential per chain.  num_ls = 0 applies the gauge and scores.
+ * xs_in: bit-packed chains holding 0|1, C_in as in rls_mcpg_metro_rounds; xs_out: bit-packed (out_spin_bytes = 0; may alias
+ * xs_in when C_in == C; a node never written holds its gauge-fixed bit) or float32 node-major [N, C] (4; a node never written
+ * holds -0.5 | 1.5, as in the reference).  edge_weights int32 [E'] in the order of g's stored edges.  visit_stream int32
+ * [stream_len] on the device (methods/MCPG.py: build_edge_stream), one record per position:
+ *     r, c, len_r, len_c, add0, add1, add2 (float32 bits), then len_r + len_c pairs (nbr | fresh << 31, weight)
+ * fresh = the neighbour has not been an endpoint of an earlier position; it is read in pass 0 only.  A record that points past N
+ * or past stream_len ends the pass; neighbour indices are clamped into the tile.
+ * uniforms f32 [num_ls, E', 3, C]: u0, u1, u2 per (pass, position) in the reference's draw order, or NULL: the counter generator
+ * (murmur3 finaliser) keyed by (seed, global chain id -- chain_ids [host], NULL = identity --, pass, position, which of the
+ * three), 24 bits to [0, 1).  expected f32 [C].  Chains past C write nothing.
+ * RLS_EUNSUPPORTED outside rls_maxcut_edge_local_search_supported (max_abs_degree and weight_abs_sum are the caller's host-side
+ * figures); RLS_EINVAL for a stream shorter than 7 E' or a gauge_node that is neither a node nor -1. */
+int rls_maxcut_edge_local_search(const rls_graph* g, const int32_t* edge_weights, const void* xs_in, int64_t C_in, void* xs_out,
+                                 int out_spin_bytes, int64_t C, const int32_t* visit_stream, int64_t stream_len, int64_t max_abs_degree,
+                                 int64_t weight_abs_sum, int gauge_node, int64_t num_ls, const float* uniforms, uint64_t seed,
+                                 float* expected, const rls_chain_ids* chain_ids, void* stream);
+
 /* --------------------------------------------------------------------- TSP */
 
 /* K12 ISCO_TSP.calculate_distance(sample)  envs/env_ISCO.py:346-350.

@@ -88,6 +88,7 @@ SIGNATURES = {
     "rls_maxsat_visit_levels": [_P, _P, _P, _I64, _I64, _P, _P, _I64, _P, _I64, _P, _P],
     "rls_maxsat_local_search": [_P, _I64, _P, _INT, _I64, _I64, _P, _P, _I64, _I64, _P, _U64, _P, _P, _P, _I64, _P, _P, _P],
     "rls_cheeger_local_search": [_G, _P, _I64, _P, _INT, _I64, _P, _I64, _INT, _I64, _F32, _P, _P, _P, _P],
+    "rls_maxcut_edge_local_search": [_G, _P, _P, _I64, _P, _INT, _I64, _P, _I64, _I64, _I64, _INT, _I64, _P, _U64, _P, _P, _P],
     "rls_graph_ell": [_P, _P, _I64, _P, _P, _I64, _P],
     "rls_graph_sweep_schedule": [_P, _P, _I64, C.c_int32, C.c_int32, _P, _P, _P, _P],
     "rls_maxcut_obj": [_G, _P, _INT, _I64, _P, _P],
@@ -157,6 +158,7 @@ PLAIN = {"rls_version": ([], _INT), "rls_device_count": ([], _INT), "rls_last_er
          "rls_qubo_local_search_supported": ([_I64, _I64, C.c_int32], _INT),
          "rls_maxsat_local_search_supported": ([_I64, _I64, _P, _P], _INT),
          "rls_cheeger_local_search_supported": ([_I64, _I64, _I64, _P], _INT),
+         "rls_maxcut_edge_local_search_supported": ([_I64, _I64, _I64, _I64, _I64, _P], _INT),
          "rls_maxcut_ls_rounds_supported": ([_G, C.c_int32], _INT),
          "rls_maxcut_node_stats_form": ([_G, _I64, C.c_int32], _INT),
          "rls_mcpg_metro_max_rounds": ([_I64, C.c_int32], _I64),

@@ -713,6 +713,40 @@ void cheeger_local_search(int64_t g, const Tensor& xs_in, int64_t C_in, Tensor x
                                 (float)edge_weight_sum, (float*)p(h), (float*)p(cut), (float*)p(size), cur_stream(xs_in)),
        "rls_cheeger_local_search");
 }
+void maxcut_edge_local_search(int64_t g, const Tensor& edge_weights, const Tensor& xs_in, int64_t C_in, Tensor xs_out, int64_t C,
+                              const Tensor& visit_stream, int64_t max_abs_degree, int64_t weight_abs_sum, int64_t gauge_node, int64_t num_ls,
+                              const OptTensor& uniforms, int64_t seed, Tensor expected, int64_t chain_offset, int64_t chain_period,
+                              int64_t chain_skip) {
+    const ChainIdsArg cid(chain_offset, chain_period, chain_skip);
+    const int64_t N = G(g)->num_nodes, E = G(g)->num_stored_edges;
+    dev(xs_in, "xs_in", I64);
+    TORCH_CHECK(C >= 0 && C_in >= 0, "C and C_in must be >= 0");
+    chain_shape(xs_in, 0, N, C_in > 0 ? C_in : C, "xs_in");
+    const int osb = chain_bytes(xs_out, "xs_out");
+    TORCH_CHECK(osb == 0 || osb == 4, "xs_out must be float32 node-major or bit-packed");
+    chain_shape(xs_out, osb, N, C, "xs_out");
+    dev(edge_weights, "edge_weights", I32);
+    count(edge_weights, "edge_weights", E);
+    dev(visit_stream, "visit_stream", I32);
+    TORCH_CHECK(visit_stream.dim() == 1 && visit_stream.numel() >= 7 * E, "visit_stream must be 1-D and hold at least 7 E = ", 7 * E,
+                " entries (one record per position), got ", visit_stream.sizes());
+    TORCH_CHECK(max_abs_degree >= 0 && weight_abs_sum >= 0, "max_abs_degree and weight_abs_sum must be >= 0");
+    TORCH_CHECK(gauge_node >= -1 && gauge_node < N, "gauge_node must be a node or -1");
+    TORCH_CHECK(num_ls >= 0, "num_ls must be >= 0");
+    optdev(uniforms, "uniforms", F32);
+    if (uniforms.has_value())
+        TORCH_CHECK(uniforms->dim() == 4 && uniforms->size(0) == num_ls && uniforms->size(1) == E && uniforms->size(2) == 3 && uniforms->size(3) == C,
+                    "uniforms must be [num_ls, E, 3, C] = [", num_ls, ", ", E, ", 3, ", C, "], got ", uniforms->sizes());
+    dev(expected, "expected", F32);
+    count(expected, "expected", C);
+    for (const Tensor* t : {(const Tensor*)&xs_out, &edge_weights, &visit_stream, (const Tensor*)&expected}) same_device(xs_in, *t, "every tensor");
+    if (uniforms.has_value()) same_device(xs_in, *uniforms, "uniforms");
+    RLS_GUARD(xs_in);
+    ok(rls_maxcut_edge_local_search(G(g), (const int32_t*)p(edge_weights), p(xs_in), C_in, p(xs_out), osb, C, (const int32_t*)p(visit_stream),
+                                    visit_stream.numel(), max_abs_degree, weight_abs_sum, (int)gauge_node, num_ls, (const float*)p(uniforms),
+                                    (uint64_t)seed, (float*)p(expected), cid.ptr(), cur_stream(xs_in)),
+       "rls_maxcut_edge_local_search");
+}
 void mcpg_pick_best(const Tensor& expected, const Tensor& xs, int64_t N, int64_t total_mcmc_num, int64_t repeat_times, int64_t num_edges,
                     Tensor best_index, Tensor vs_good, Tensor xs_good) {
     dev(expected, "expected", F32);
@@ -1077,6 +1111,9 @@ TORCH_LIBRARY(rlsolver_hip, m) {
           "int seed, Tensor clause_ptr, Tensor lit, Tensor? weight, Tensor(b!) expected, int chain_offset=0, int chain_period=0, int chain_skip=0) -> ()");
     m.def("cheeger_local_search(int graph, Tensor xs_in, int C_in, Tensor(a!) xs_out, int C, Tensor visit_stream, int normalized, int num_ls, "
           "float edge_weight_sum, Tensor(b!) h, Tensor(c!)? cut=None, Tensor(d!)? size=None) -> ()");
+    m.def("maxcut_edge_local_search(int graph, Tensor edge_weights, Tensor xs_in, int C_in, Tensor(a!) xs_out, int C, Tensor visit_stream, "
+          "int max_abs_degree, int weight_abs_sum, int gauge_node, int num_ls, Tensor? uniforms, int seed, Tensor(b!) expected, "
+          "int chain_offset=0, int chain_period=0, int chain_skip=0) -> ()");
     m.def("isco_mis_step(int graph, Tensor x, Tensor(a!) y_out, Tensor path_length, float temperature, float lam, Tensor? u_gumbel, Tensor? u_accept, "
           "int seed, int env_offset, Tensor(b!)? energy_out, Tensor(c!)? acc_out, Tensor(d!)? terms_out, Tensor(e!)? mask_out, Tensor(f!)? scratch=None) -> ()");
     m.def("isco_tsp_step(Tensor dist, Tensor nearest, float near_threshold, Tensor random, Tensor perm_in, Tensor(a!) perm_out, int path_length, "
@@ -1137,5 +1174,6 @@ TORCH_LIBRARY_IMPL(rlsolver_hip, CUDA, m) {   // "CUDA" is the HIP dispatch key 
     m.impl("isco_mis_step", &isco_mis_step);
     m.impl("maxsat_local_search", &maxsat_local_search);
     m.impl("cheeger_local_search", &cheeger_local_search);
+    m.impl("maxcut_edge_local_search", &maxcut_edge_local_search);
     m.impl("isco_tsp_step", &isco_tsp_step);
 }

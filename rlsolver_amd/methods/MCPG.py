@@ -217,6 +217,58 @@ def build_cheeger_stream(csr, order: np.ndarray) -> np.ndarray:
     return stream.astype(np.int32)
 
 
+def edge_rows(num_nodes: int, eu: np.ndarray, ev: np.ndarray, w: np.ndarray):
+    """The symmetric neighbour rows of dataloader.py:106-123 as a CSR (rowptr, col, wt) in STORED-EDGE order: edge k appends
+    (ev[k], w[k]) to row eu[k] and then (eu[k], w[k]) to row ev[k], so a self-loop lists its node twice."""
+    eu, ev, w = (np.asarray(a, dtype=np.int64) for a in (eu, ev, w))
+    E = eu.shape[0]
+    rows = np.concatenate([eu, ev])
+    seq = np.concatenate([2 * np.arange(E), 2 * np.arange(E) + 1])
+    o = np.lexsort((seq, rows))
+    rowptr = np.concatenate([[0], np.cumsum(np.bincount(rows, minlength=num_nodes))]).astype(np.int64)
+    return rowptr, np.concatenate([ev, eu])[o], np.concatenate([w, w])[o]
+
+
+def build_edge_stream(num_nodes: int, eu, ev, w, order: np.ndarray, add: np.ndarray) -> np.ndarray:
+    """Flatten the visiting order of the edge-flip MaxCut sweep (format: include/rlsolver_hip.h: rls_maxcut_edge_local_search):
+    int32, one record per position i (edge e = order[i], r = eu[e], c = ev[e]) --
+        r, c, len_r, len_c, add[0][e], add[1][e], add[2][e] (float32 bits), then len_r + len_c pairs (nbr | fresh << 31, weight):
+    row(r) less its FIRST entry c (the earliest stored edge joining r and c in either direction, with its weight: not necessarily
+    e), then row(c) less its first entry r (dataloader.py:125-153).  fresh = the neighbour has not been an endpoint of an earlier
+    position (it still holds -0.5 | 1.5 when this position reads it in pass 0).  The sweep is sequential per chain: the records
+    simply follow the order."""
+    eu, ev, w = (np.asarray(a, dtype=np.int64) for a in (eu, ev, w))
+    E = eu.shape[0]
+    order = np.asarray(order, dtype=np.int64)
+    if order.shape != (E,) or not np.array_equal(np.sort(order), np.arange(E)):
+        raise ValueError("order must be a permutation of the edges")
+    add_bits = np.ascontiguousarray(add, dtype=np.float32).view(np.int32).astype(np.int64)
+    if add_bits.shape != (3, E):
+        raise ValueError("add must be [3, E]")
+    rowptr, col, wt = edge_rows(num_nodes, eu, ev, w)
+    first = np.full(num_nodes, E, dtype=np.int64)                 # position of a node's first write
+    np.minimum.at(first, eu[order], np.arange(E))
+    np.minimum.at(first, ev[order], np.arange(E))
+
+    def row_less(a: int, b: int) -> np.ndarray:
+        lo, hi = int(rowptr[a]), int(rowptr[a + 1])
+        k = lo + int(np.argmax(col[lo:hi] == b))                   # (b is always there: edge e itself put it)
+        return np.concatenate([np.arange(lo, k), np.arange(k + 1, hi)])
+
+    recs = []
+    for i, e in enumerate(order):
+        r, c = int(eu[e]), int(ev[e])
+        ir, ic = row_less(r, c), row_less(c, r)
+        idx = np.concatenate([ir, ic])
+        rec = np.empty(7 + 2 * idx.shape[0], dtype=np.int64)
+        rec[:7] = (r, c, ir.shape[0], ic.shape[0], add_bits[0, e], add_bits[1, e], add_bits[2, e])
+        rec[7::2] = col[idx] | ((first[col[idx]] >= i).astype(np.int64) << 31)
+        rec[8::2] = wt[idx]
+        recs.append(rec)
+    stream = np.concatenate(recs) if recs else np.zeros(0, dtype=np.int64)
+    return (stream & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+
+
 ACCEPT_ROWS = 64      # rows the kernels spread their per-round accept counts over (one row = thousands of atomics per address)
 
 

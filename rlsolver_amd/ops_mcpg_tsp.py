@@ -250,6 +250,40 @@ def mcpg_cheeger_local_search(g: DeviceGraph, xs_in: PackedChains, visit_stream:
     return xs_out, h, cut, size
 
 
+def mcpg_maxcut_edge_local_search(g: DeviceGraph, edge_weights: TEN, xs_in: PackedChains, visit_stream: TEN, max_abs_degree: int,
+                                  weight_abs_sum: int, num_ls: int, gauge_node: int = -1, uniforms: Optional[TEN] = None, seed: int = 0,
+                                  out=None, num_chains: Optional[int] = None, chain_ids=None):
+    """Gauge fix, sweep and score of the edge-flip MaxCut sampler (include/rlsolver_hip.h: rls_maxcut_edge_local_search).
+    ``xs_in``: PackedChains over the nodes (may hold fewer chains than ``num_chains``, a multiple of 64: broadcast);
+    ``edge_weights`` int32 [E'] in the order of the graph's stored edges; ``visit_stream`` int32: the records of
+    methods/MCPG.py: build_edge_stream; ``max_abs_degree`` / ``weight_abs_sum``: the largest sum of |weights| at a node and the
+    sum over the edges (the exactness limits are checked on them); ``gauge_node``: the hub every chain is XORed with, -1 = none.
+    ``uniforms`` f32 [num_ls, E', 3, C]: the three draws per (pass, position) -- test hook; None = counter hash keyed by seed and
+    the global chain id (``chain_ids``).  ``out``: a PackedChains to write (may be xs_in itself) or None = node-major f32, where a
+    node no position writes holds -0.5 | 1.5.  ``num_ls = 0`` applies the gauge and scores.
+    Returns (xs_out, expected f32 [C])."""
+    if not isinstance(xs_in, PackedChains):
+        raise TypeError("xs_in must be a PackedChains")
+    dev, N = xs_in.device, xs_in.num_nodes
+    if dev != g.device or N != g.num_nodes:
+        raise ValueError(f"xs_in must hold {g.num_nodes} nodes on {g.device}")
+    Cc = xs_in.num_chains if num_chains is None else num_chains
+    _check(edge_weights, "edge_weights", (torch.int32,), dev, (g.num_stored_edges,))
+    _check(visit_stream, "visit_stream", (torch.int32,), dev)
+    if uniforms is not None:
+        _check(uniforms, "uniforms", (torch.float32,), dev, (num_ls, g.num_stored_edges, 3, Cc))
+    if out is None:
+        xs_out = ot = torch.empty((N, Cc), dtype=torch.float32, device=dev)
+    else:
+        if not isinstance(out, PackedChains) or out.num_chains != Cc or out.num_nodes != N or out.device != dev:
+            raise ValueError("out must be a PackedChains of num_chains chains")
+        xs_out, ot = out, out.words
+    expected = torch.empty(Cc, dtype=torch.float32, device=dev)
+    _t.maxcut_edge_local_search(g.handle, edge_weights, xs_in.words, xs_in.num_chains, ot, Cc, visit_stream, int(max_abs_degree),
+                                int(weight_abs_sum), int(gauge_node), int(num_ls), uniforms, _s64(seed), expected, *_chain_ids(chain_ids))
+    return xs_out, expected
+
+
 def mcpg_pick_best(expected: TEN, xs, total_mcmc_num: int, repeat_times: int, num_edges: int):
     """K8 second half.  Returns (best_index int64 [M], vs_good f32 [M], xs_good: f32 [N, M] or PackedChains of M chains)."""
     st, sb, N, Cc = _chains(xs, "xs")

@@ -1845,7 +1845,104 @@ def gen_cheeger():
     save("cheeger", **out)
 
 
-ALL = {"graph_forms": gen_graph_forms, "cheeger": gen_cheeger, "maxsat": gen_maxsat, "mcpg_weighted": gen_mcpg_weighted, "isco_steps": gen_isco_steps, "isco_mis": gen_isco_mis, "spinsystem_cpu": gen_spinsystem_cpu, "spinsystem": gen_spinsystem, "spinsystem_perenv": gen_spinsystem_perenv, "qubo": gen_qubo, "qubo_asym": gen_qubo_asym, "isco_maxcut": gen_isco_maxcut, "maxcut": gen_maxcut, "sweep": gen_sweep, "lsclass": gen_local_search_class, "ppo": gen_ppo,
+EDGE_GRAPHS = ("BA_5_ID0", "PL_20_ID0", "BA_100_ID0", "gset_14_stub")
+EDGE_CONFIGS = ((5, 3), (64, 2))            # (total_mcmc_num, repeat_times); the second only where its draws fit the fixture
+EDGE_SMALL = 40                             # edges: graphs up to this size also take the 64 x 2 configuration
+# written graphs, kept as the text of their files (1-based endpoints): signed weights, parallel edges of different weights
+# (2-3 twice), a reversed duplicate (5 4 after 4 5), a self-loop (7 7), an isolated node (12), and the one-edge graph
+EDGE_WRITTEN = {
+    "signed_12": "12 16\n1 2 3\n2 3 -2\n2 3 5\n3 4 1\n4 5 -1\n5 4 2\n5 6 4\n6 7 -3\n7 7 2\n7 8 1\n8 9 -4\n9 10 2\n10 11 -1\n11 1 3\n"
+                 "1 6 -2\n3 9 1\n",
+    "one_edge": "2 1\n1 2 1\n",
+}
+
+
+def gen_maxcut_edge():
+    """mcpg_sampling_maxcut_edge (rlsolver/methods/MCPG/sampling.py:130-178) run on CPU on graphs loaded by the package's own
+    maxcut_dataloader (dataloader.py:53-160), every draw recorded.  The sampler asks for its three draws per edge on a fixed
+    accelerator: ``device=`` is stripped from torch.rand while recording.  The same seed precedes the num_ls = 1 and the num_ls = 2
+    call, so both see the same walk and the first call's draws are a prefix of the second's: they are stored once."""
+    import tempfile
+    smp = _load_upstream_mcpg("sampling")
+    dl = _load_upstream_mcpg("dataloader")
+    cpu = th.device("cpu")
+    bits = lambda t: np.packbits(u8(t), axis=0)      # noqa: E731
+    out, names, cases = {}, [], []
+    sources = [(g, os.path.join(DATA, GRAPHS[g]), None) for g in EDGE_GRAPHS] + [(g, None, t) for g, t in EDGE_WRITTEN.items()]
+    for gi, (gname, path, text) in enumerate(sources):
+        if text is not None:
+            with tempfile.NamedTemporaryFile("w", suffix=".txt", delete=False) as f:
+                f.write(text)
+                path = f.name
+            out[f"{gname}/text"] = np.array(text)
+        data, n = dl.maxcut_dataloader(path, device=cpu)
+        if text is not None:
+            os.unlink(path)
+        E = data.edge_index.shape[1]
+        names.append(gname)
+        out[f"{gname}/edges"] = data.edge_index.numpy().astype(np.int32)
+        out[f"{gname}/weights"] = data.edge_attr[:, 0].numpy().astype(np.int32)
+        out[f"{gname}/num_nodes"] = np.int64(n)
+        out[f"{gname}/edge_weight_sum"] = np.float64(data.edge_weight_sum)
+        out[f"{gname}/sorted_degree_nodes"] = data.sorted_degree_nodes.numpy().astype(np.int32)
+        out[f"{gname}/sorted_degree_edges"] = data.sorted_degree_edges.numpy().astype(np.int32)
+        out[f"{gname}/add"] = data.add.numpy().copy()
+        for ci, (M, R) in enumerate(EDGE_CONFIGS):
+            if ci > 0 and E > EDGE_SMALL:
+                continue
+            C = M * R
+            g = th.Generator().manual_seed(5100 + 10 * gi + ci)
+            probs = th.rand(n, generator=g) * 0.6 + 0.2
+            start = th.randint(0, 2, (n, C), generator=g).float()
+            change_times = max(1, n // 10)
+            key = f"{gname}/{M}x{R}"
+            walk = None
+            for num_ls in (1, 2):
+                th.manual_seed(5200 + 10 * gi + ci)
+                log = {"rand": [], "randint": []}
+                orig_rand, orig_randint = th.rand, th.randint
+
+                def rand(*a, **k):
+                    k.pop("device", None)
+                    r = orig_rand(*a, **k)
+                    log["rand"].append(r.detach().clone())
+                    return r
+
+                def randint(*a, **k):
+                    r = orig_randint(*a, **k)
+                    log["randint"].append(r.detach().clone())
+                    return r
+
+                th.rand, th.randint = rand, randint
+                try:
+                    res, best, raw, value = smp.mcpg_sampling_maxcut_edge(data, start.clone(), probs, num_ls, change_times, M, device=cpu)
+                finally:
+                    th.rand, th.randint = orig_rand, orig_randint
+                T = len(log["randint"])
+                assert len(log["rand"]) == T + 3 * E * num_ls
+                index = th.stack(log["randint"]).numpy().astype(np.int16)
+                u = th.stack(log["rand"][:T]).numpy().copy()
+                uni = th.stack(log["rand"][T:]).numpy().copy().reshape(num_ls, E, 3, C)
+                if walk is None:
+                    walk = (index, u, u8(raw), uni)
+                    out[f"{key}/probs"], out[f"{key}/start"] = probs.numpy().copy(), bits(start)
+                    out[f"{key}/change_times"] = np.int64(change_times)
+                    out[f"{key}/index"], out[f"{key}/u"], out[f"{key}/raw"] = index, u, bits(raw)
+                else:
+                    assert np.array_equal(walk[0], index) and np.array_equal(walk[1], u) and np.array_equal(walk[2], u8(raw))
+                    assert np.array_equal(walk[3], uni[:1])
+                    out[f"{key}/uniforms"] = uni
+                t = f"{key}/ls{num_ls}"
+                cases.append(t)
+                out[f"{t}/res"], out[f"{t}/best"], out[f"{t}/value"] = res.numpy().copy(), best.numpy().copy(), value.numpy().copy()
+    out["names"], out["cases"] = np.array(names), np.array(cases)
+    out["source"] = np.array("recorded from the reference's own maxcut_dataloader and mcpg_sampling_maxcut_edge on CPU (device= stripped "
+                             "from its torch.rand calls); start / raw as np.packbits(axis=0) of the [N, C] 0|1 arrays, best as float32 "
+                             "(a node no edge touches holds -0.5 | 1.5), uniforms [2, E, 3, C] in draw order (temp[1], temp[2], temp[0])")
+    save("maxcut_edge", **out)
+
+
+ALL = {"graph_forms": gen_graph_forms, "cheeger": gen_cheeger, "maxcut_edge": gen_maxcut_edge, "maxsat": gen_maxsat, "mcpg_weighted": gen_mcpg_weighted, "isco_steps": gen_isco_steps, "isco_mis": gen_isco_mis, "spinsystem_cpu": gen_spinsystem_cpu, "spinsystem": gen_spinsystem, "spinsystem_perenv": gen_spinsystem_perenv, "qubo": gen_qubo, "qubo_asym": gen_qubo_asym, "isco_maxcut": gen_isco_maxcut, "maxcut": gen_maxcut, "sweep": gen_sweep, "lsclass": gen_local_search_class, "ppo": gen_ppo,
        "select": gen_select, "mcpg": gen_mcpg, "tsp": gen_tsp, "tsp_2opt": gen_tsp_2opt, "encoder": gen_encoder,
        "wgain": gen_weighted_gain, "mcpg_glue": gen_mcpg_glue, "evaluator": gen_evaluator, "spinsystem_options": gen_spinsystem_options,
        "api_surface": gen_api_surface, "mcpg_data": gen_mcpg_data,
