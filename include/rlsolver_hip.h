@@ -708,6 +708,26 @@ int rls_qubo_sparse_local_search_value(const int32_t* rowptr, const int32_t* col
  * nnz = 0 -- the sparse one with a level schedule built over the symmetrised pattern (Q_ij != 0 or Q_ji != 0). */
 int rls_qubo_local_search_supported(int64_t n, int64_t C, int32_t form);
 
+/* K12 mcpg_sampling_mimo  methods/MCPG/sampling.py:296-313 (after the metro step): the MIMO detection sampler's coordinate
+ * search and value on K11's block scheme (additive: the ABI stays v12).  Sigma f32 [n, n] dense (any square matrix: the diagonal
+ * is NOT masked, the reference's loaders zero it), Diag f32 [n].  Chains bit-packed tile-major uint64 [ceil(C / 64), n] (bit 1 =
+ * +, bit 0 = -); xs_in may hold C_in < C chains, C_in a multiple of 64: chain c reads chain c % C_in (C_in <= 0 = C); xs_out may
+ * be xs_in when C_in == C; bits of chains past C leave as 0.
+ *   info = +-2 (every variable, before its first visit);  num_ls sweeps over i = 0 .. n-1:
+ *     r = Sigma[i, :] . info  (the current info, info_i included);  info_i = +1 if r < -Diag_i / 2 else -1  (strict: a tie is -1)
+ *   expected[c] = sum_i info_i (Sigma info)_i + Diag . info      (to be MINIMISED; the reference returns -(min + sca)).
+ * f32 in, f32 accumulate on the matrix cores; sums run in another order than the reference's matmul.  Bit-exact with it for
+ * integer-valued Sigma / Diag when  2 sum_j |Sigma_ij| + |Diag_i| < 2^24  for every row i and  sum |Sigma| + sum |Diag| < 2^24.
+ * num_ls < 1 is RLS_EINVAL (+-2 entries would survive).  xs_out == NULL: no sweep, nothing written but expected of the chains
+ * as +-1 (num_ls is not read).  n beyond the LDS budget (rls_mimo_local_search_supported) is RLS_EUNSUPPORTED. */
+int rls_mimo_local_search(const float* Sigma, const float* Diag, int64_t n, const uint64_t* xs_in, int64_t C_in, uint64_t* xs_out,
+                          int64_t C, int64_t num_ls, float* expected, void* stream);
+
+/* [host] 1 when rls_mimo_local_search runs n >= 1 variables x C chains within its LDS budget (K11's: n <= 30 720 / 35 840 /
+ * 15 872 by form), else 0.  *form (may be NULL) = the launch form this shape gets, chosen by K11's rule from C and the CU count:
+ * 0 = 32-chain workgroups of 8 waves, 1 = 32-chain workgroups of 4 waves, 2 = 64-chain workgroups of 4 waves. */
+int rls_mimo_local_search_supported(int64_t n, int64_t C, int32_t* form);
+
 /* ------------------------------------------------------------------ MaxSAT */
 
 /* [host] Level schedule of mcpg_sampling_maxsat's sweep  methods/MCPG/sampling.py:259-271 (additive: the ABI stays v12).

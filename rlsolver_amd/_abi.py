@@ -128,6 +128,7 @@ SIGNATURES = {
     "rls_mcpg_unpack_chains": [_P, _I64, _I64, _P, _P],
     "rls_qubo_local_search_value": [_P, _I64, _P, _P, _I64, _I64, _INT, _P, _P],
     "rls_qubo_sparse_local_search_value": [_P, _P, _P, _I64, _P, _P, C.c_int32, _P, _P, _I64, _I64, _INT, _P, _P],
+    "rls_mimo_local_search": [_P, _P, _I64, _P, _I64, _P, _I64, _I64, _P, _P],
     "rls_tsp_tour_length": [_P, _I64, _P, _I64, _P, _P],
     "rls_tsp_swap_delta_all": [_P, _I64, _P, _I64, _P, _P, C.c_int32, _P, C.c_int32, _P, _F32, C.c_uint64, _I64, _P, _F32, _P, _P, _P, _P],
     "rls_tsp_apply_swap": [_P, _I64, _I64, _P, _P, _P],
@@ -156,6 +157,7 @@ PLAIN = {"rls_version": ([], _INT), "rls_device_count": ([], _INT), "rls_last_er
          "rls_maxcut_local_search_supported": ([_G, _I64, C.c_int32], _INT),
          "rls_mcpg_local_search_levels_supported": ([_G, _I64], _INT),
          "rls_qubo_local_search_supported": ([_I64, _I64, C.c_int32], _INT),
+         "rls_mimo_local_search_supported": ([_I64, _I64, _P], _INT),
          "rls_maxsat_local_search_supported": ([_I64, _I64, _P, _P], _INT),
          "rls_cheeger_local_search_supported": ([_I64, _I64, _I64, _P], _INT),
          "rls_maxcut_edge_local_search_supported": ([_I64, _I64, _I64, _I64, _I64, _P], _INT),

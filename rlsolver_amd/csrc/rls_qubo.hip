@@ -49,7 +49,10 @@ __device__ __forceinline__ float qm_spin(uint32_t word, int c) {
 
 // acc[.] += Q[i0 + r, k] * s[k, chains] over the batches [kb0, kb1) (multiples of 32) of this wave.
 // NT = 1: acc[0] / acc[1] take the even / odd MFMAs of the one chain tile; NT = 2: acc[t] is chain tile t.
-template <bool BIN, int NT, bool MASK_DIAG>
+// MIMO (0 for K11; the MIMO kernel below): 2 = its first sweep, where the columns k >= i0 count twice -- their variables still
+// hold +-2; 1 = its other calls, which compute what K11's do but take instantiations of their own: sharing them changed K11's
+// register allocation.
+template <bool BIN, int NT, bool MASK_DIAG, int MIMO = 0>
 __device__ __forceinline__ void qm_block_dot(const float* __restrict__ Q, int64_t n, int64_t i0, int64_t kb0, int64_t kb1,
                                              const typename QmWord<NT>::type* __restrict__ words, int r, int h,
                                              f32x16 (&acc)[2]) {
@@ -81,6 +84,10 @@ __device__ __forceinline__ void qm_block_dot(const float* __restrict__ Q, int64_
 #pragma unroll
             for (int e = 0; e < 16; ++e)
                 if (kk + e == row) a[e] = 0.0f;
+        }
+        if (MIMO == 2 && kb >= i0) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) a[e] *= 2.0f;          // exact
         }
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
@@ -235,6 +242,169 @@ __global__ __launch_bounds__(W * kWave) void k_qubo_ls_value_mfma(const float* _
     } else {
         if (c0 + r < C)
             for (int64_t j = (int64_t)w * 2 + h; j < n; j += (int64_t)W * 2) xs_out[j * C + c0 + r] = (float)((words[j] >> r) & 1u);
+    }
+}
+
+// The MIMO kernel: the coordinate search + value of the MIMO detection sampler (MCPG/sampling.py:296-313) on K11's block scheme -- the same
+// GEMM per 32-variable block (qm_block_dot), the same in-order resolution by rank-1 MFMAs, the same three launch forms (qm_plan).
+// What differs from K11, all of it in this body:
+//   * the chains arrive and leave BIT-PACKED (tile-major uint64 [ceil(C / 64), n]): a tile row is already the LDS word
+//     (NT = 2), or one 32-bit half of it (NT = 1: workgroup b takes half b % 2 of tile b / 2) -- the tile load is a copy;
+//   * a variable holds +-2 until its first visit: sweep 0 (FIRST) doubles the A operand of the columns k >= i0 and resolves
+//     with delta = new (+-1) - old (+-2); every later sweep runs the +-1 instantiation and pays nothing for it;
+//   * the product includes Sigma_ii info_i (nothing is masked), the decision is  r < -Diag_i / 2  (strict: a tie gives -1),
+//     and the value adds Diag . info.
+template <int NT, int W>
+__global__ __launch_bounds__(W * kWave) void k_mimo_ls_value_mfma(const float* __restrict__ Sigma, const float* __restrict__ Diag,
+                                                                  int64_t n, int64_t n_pad, const uint64_t* xs_in, int64_t tiles_in,
+                                                                  uint64_t* xs_out, int64_t C, int64_t num_ls,
+                                                                  float* __restrict__ expected) {
+    using Word = typename QmWord<NT>::type;
+    constexpr int PS = qm_part_stride<NT>();
+    constexpr int CH = 32 * NT;                                  // chains per workgroup
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    Word* words = reinterpret_cast<Word*>(smem);                                 // [n_pad] bit c = chain c0 + c
+    float* part = reinterpret_cast<float*>(words + n_pad);                       // [W][32][PS]
+    const int tid = threadIdx.x;
+    const int lane = tid & (kWave - 1);
+    const int w = __builtin_amdgcn_readfirstlane((int)(tid / kWave));
+    const int r = lane & 31, h = lane >> 5;                      // r doubles as the chain column of B / D
+    const int64_t tile = NT == 2 ? (int64_t)blockIdx.x : (int64_t)(blockIdx.x >> 1);
+    const int half = NT == 2 ? 0 : (int)(blockIdx.x & 1);
+    const int64_t c0 = tile * kWave + 32 * half;
+    const int64_t left = C - c0;                                 // live chains of this workgroup; chains past C read and leave as 0
+    const Word live = left >= CH ? ~(Word)0 : (left > 0 ? (Word)(((Word)1 << left) - 1) : (Word)0);
+    uint32_t* out32 = reinterpret_cast<uint32_t*>(xs_out) + 2 * tile * n + half;             // NT = 1: this half of word j is out32[2 j]
+    if (NT == 1 && left <= 0) {                                  // the empty upper half of a ragged last tile
+        if (xs_out)
+            for (int64_t j = tid; j < n; j += W * kWave) out32[2 * j] = 0u;
+        return;
+    }
+    {
+        const uint64_t* src = xs_in + (tile % tiles_in) * n;
+        const uint32_t* src32 = reinterpret_cast<const uint32_t*>(src) + half;
+        for (int64_t j = tid; j < n_pad; j += W * kWave) {
+            Word wd = 0;
+            if (j < n) {
+                if constexpr (NT == 2) wd = src[j];
+                else wd = src32[2 * j];
+            }
+            words[j] = wd & live;
+        }
+    }
+    __syncthreads();
+    const int64_t kper = n_pad / W;                              // a multiple of 32
+    const int64_t kb0 = (int64_t)w * kper, kb1 = kb0 + kper;
+    float* mypart = part + (size_t)w * 32 * PS;
+    auto tile_word = [&](Word wd, int t) -> uint32_t { return NT == 1 ? (uint32_t)wd : (uint32_t)((uint64_t)wd >> (32 * t)); };
+    auto sweep = [&](auto first) {
+        constexpr bool FIRST = decltype(first)::value;
+        for (int64_t i0 = 0; i0 < n; i0 += 32) {
+            // wave 0 fetches its rows of the block's 32 x 32 corner of Sigma and the block's Diag (lane (r, .): row i0 + r)
+            float qc[32];
+            float thr = 0.0f;
+            if (w == 0) {
+                const int64_t row = i0 + r;
+                if (row < n && i0 + 32 <= n) {
+#pragma unroll
+                    for (int q4 = 0; q4 < 8; ++q4) {
+                        const f32x4u v = *reinterpret_cast<const f32x4u*>(Sigma + row * n + i0 + 4 * q4);
+                        qc[4 * q4] = v.x; qc[4 * q4 + 1] = v.y; qc[4 * q4 + 2] = v.z; qc[4 * q4 + 3] = v.w;
+                    }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 32; ++k) qc[k] = (row < n && i0 + k < n) ? Sigma[row * n + i0 + k] : 0.0f;
+                }
+                thr = row < n ? -Diag[row] / 2.0f : 0.0f;        // an exact halving
+            }
+            f32x16 acc[2] = {{0}, {0}};
+            qm_block_dot<false, NT, false, FIRST ? 2 : 1>(Sigma, n, i0, kb0, kb1, words, r, h, acc);
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                float* dst = mypart + (8 * (v / 4) + 4 * h + (v % 4)) * PS + r;
+                if constexpr (NT == 1) dst[0] = acc[0][v] + acc[1][v];
+                else { dst[0] = acc[0][v]; dst[32] = acc[1][v]; }
+            }
+            __syncthreads();
+            if (w == 0) {
+                // K11's resolution: step k reads row k of R, decides, and updates R by one MFMA per chain tile; the update also
+                // lands on row k itself (the diagonal is not masked), which nobody reads again
+                const int kbk = (int)((n - i0) < 32 ? (n - i0) : 32);
+                f32x16 R[NT];
+#pragma unroll
+                for (int t = 0; t < NT; ++t)
+#pragma unroll
+                    for (int v = 0; v < 16; ++v) {
+                        float sum = 0.0f;
+#pragma unroll
+                        for (int ww = 0; ww < W; ++ww) sum += part[(size_t)(ww * 32 + 8 * (v / 4) + 4 * h + (v % 4)) * PS + 32 * t + r];
+                        R[t][v] = sum;
+                    }
+                Word mine = 0;                                   // lane k ends up with the new word of variable i0 + k
+#pragma unroll
+                for (int k = 0; k < 32; ++k) {
+                    const int hk = (k / 4) & 1;
+                    const float thr_k = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, thr), k));
+                    const Word old = words[i0 + k];              // the tile keeps the OLD bits until the block is resolved
+                    Word nw = 0;
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) {
+                        const bool nb = R[t][4 * (k / 8) + (k % 4)] < thr_k;      // +1 if r < -Diag / 2 else -1
+                        const uint64_t bal = ballot64(nb);
+                        nw |= (Word)(hk ? (uint32_t)(bal >> 32) : (uint32_t)bal) << (NT == 1 ? 0 : 32 * t);
+                        const uint32_t ob = (tile_word(old, t) >> r) & 1u;
+                        float d = FIRST ? ((nb ? 1.0f : -1.0f) - (ob ? 2.0f : -2.0f)) : ((float)nb - (float)ob) * 2.0f;
+                        if (h != hk) d = 0.0f;
+                        R[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(qc[k], d, R[t], 0, 0, 0);
+                    }
+                    if (lane == k) mine = nw;
+                }
+                if (lane < kbk) words[i0 + lane] = mine;
+            }
+            __syncthreads();
+        }
+    };
+    if (num_ls > 0) sweep(std::true_type{});
+    for (int64_t cnt = 1; cnt < num_ls; ++cnt) sweep(std::false_type{});
+    // expected[c] = sum_i s_i ((Sigma s)_i + Diag_i): every wave weighs its partial products with the rows' spins, wave 0 adds Diag
+    float total[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) total[t] = 0.0f;
+    for (int64_t i0 = 0; i0 < n; i0 += 32) {
+        f32x16 acc[2] = {{0}, {0}};
+        qm_block_dot<false, NT, false, 1>(Sigma, n, i0, kb0, kb1, words, r, h, acc);
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+            const int64_t row = i0 + 8 * (v / 4) + 4 * h + (v % 4);
+            const Word wd = words[row];
+            const float dg = (w == 0 && row < n) ? Diag[row] : 0.0f;
+            if constexpr (NT == 1) total[0] += qm_spin<false>(wd, r) * ((acc[0][v] + acc[1][v]) + dg);
+            else {
+                total[0] += qm_spin<false>((uint32_t)wd, r) * (acc[0][v] + dg);
+                total[1] += qm_spin<false>((uint32_t)(wd >> 32), r) * (acc[1][v] + dg);
+            }
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const float both = total[t] + __shfl_xor(total[t], 32, 64);
+        if (h == 0) part[(w * NT + t) * 32 + r] = both;
+    }
+    __syncthreads();
+    if (w == 0 && lane < CH && c0 + lane < C) {
+        float sum = 0.0f;
+#pragma unroll
+        for (int k = 0; k < W; ++k) sum += part[(k * NT + (lane >> 5)) * 32 + r];
+        expected[c0 + lane] = sum;
+    }
+    if (xs_out) {
+        if constexpr (NT == 2) {
+            uint64_t* dst = xs_out + tile * n;
+            for (int64_t j = tid; j < n; j += W * kWave) dst[j] = words[j] & live;
+        } else {
+            for (int64_t j = tid; j < n; j += W * kWave) out32[2 * j] = words[j] & live;
+        }
     }
 }
 
@@ -562,6 +732,40 @@ extern "C" int rls_qubo_local_search_value(const float* Q, int64_t n, const floa
     }
 #undef RLS_QM_LAUNCH
     return check_launch("k_qubo_ls_value_mfma");
+}
+
+extern "C" int rls_mimo_local_search_supported(int64_t n, int64_t C, int32_t* form) {
+    if (n < 1 || C < 0) return 0;
+    const QmPlan pl = qm_plan(n, C);
+    if (form) *form = pl.nt2 ? 2 : (pl.W == 8 ? 0 : 1);
+    return pl.lds <= (size_t)kLdsBytes;
+}
+
+extern "C" int rls_mimo_local_search(const float* Sigma, const float* Diag, int64_t n, const uint64_t* xs_in, int64_t C_in,
+                                     uint64_t* xs_out, int64_t C, int64_t num_ls, float* expected, void* stream) {
+    RLS_REQUIRE(n > 0 && C >= 0, RLS_EINVAL, "bad sizes n=%lld C=%lld", (long long)n, (long long)C);
+    // xs_out == NULL scores the chains as they are (+-1, no sweep; num_ls is not read): what Data_MIMO.result needs
+    RLS_REQUIRE(!xs_out || num_ls >= 1, RLS_EINVAL, "num_ls=%lld: a sweep-less call would leave +-2 entries (num_ls >= 1)",
+                (long long)num_ls);
+    const QmPlan pl = qm_plan(n, C);
+    RLS_REQUIRE(pl.lds <= (size_t)kLdsBytes, RLS_EUNSUPPORTED, "n=%lld needs %zu B of LDS (max %d)", (long long)n, pl.lds, kLdsBytes);
+    if (C == 0) return RLS_OK;
+    RLS_REQUIRE(Sigma && Diag && xs_in && expected, RLS_EINVAL, "NULL pointer");
+    if (C_in <= 0) C_in = C;
+    RLS_REQUIRE(C_in == C || (C_in % kWave == 0 && C_in < C), RLS_EINVAL, "broadcast input (C_in != C) needs C_in a multiple of 64 below C");
+    RLS_REQUIRE(xs_in != xs_out || C_in == C, RLS_EINVAL, "in-place needs C_in == C");
+    const int64_t tiles = ceil_div(C, kWave), tiles_in = ceil_div(C_in, kWave);
+    RLS_REQUIRE(tiles < (1ll << 30), RLS_EINVAL, "too many chains");
+    const dim3 grid((unsigned)(pl.nt2 ? tiles : 2 * tiles)), block(pl.W * kWave);
+    const int64_t sweeps = xs_out ? num_ls : 0;
+    auto launch = [&](auto kern) {
+        ensure_dyn_lds((const void*)kern, pl.lds);
+        hipLaunchKernelGGL(kern, grid, block, pl.lds, as_stream(stream), Sigma, Diag, n, pl.n_pad, xs_in, tiles_in, xs_out, C, sweeps, expected);
+    };
+    if (pl.nt2) launch(k_mimo_ls_value_mfma<2, 4>);
+    else if (pl.W == 8) launch(k_mimo_ls_value_mfma<1, 8>);
+    else launch(k_mimo_ls_value_mfma<1, 4>);
+    return check_launch("k_mimo_ls_value_mfma");
 }
 
 extern "C" int rls_qubo_sparse_local_search_value(const int32_t* rowptr, const int32_t* col, const float* val, int64_t n,

@@ -747,6 +747,29 @@ void maxcut_edge_local_search(int64_t g, const Tensor& edge_weights, const Tenso
                                     (uint64_t)seed, (float*)p(expected), cid.ptr(), cur_stream(xs_in)),
        "rls_maxcut_edge_local_search");
 }
+void mimo_local_search(const Tensor& Sigma, const Tensor& Diag, const Tensor& xs_in, int64_t C_in, const OptTensor& xs_out, int64_t C,
+                       int64_t num_ls, Tensor expected) {
+    dev(Sigma, "Sigma", F32);
+    TORCH_CHECK(Sigma.dim() == 2 && Sigma.size(0) == Sigma.size(1) && Sigma.size(0) >= 1, "Sigma must be square [n, n], got ", Sigma.sizes());
+    const int64_t n = Sigma.size(0);
+    dev(Diag, "Diag", F32);
+    count(Diag, "Diag", n);
+    dev(xs_in, "xs_in", I64);
+    TORCH_CHECK(C >= 0 && C_in >= 0, "C and C_in must be >= 0");
+    chain_shape(xs_in, 0, n, C_in > 0 ? C_in : C, "xs_in");
+    optdev(xs_out, "xs_out", I64);
+    if (xs_out.has_value()) {
+        chain_shape(*xs_out, 0, n, C, "xs_out");
+        same_device(Sigma, *xs_out, "xs_out");
+        TORCH_CHECK(num_ls >= 1, "num_ls must be >= 1 (a sweep-less call would leave +-2 entries), got ", num_ls);
+    }
+    dev(expected, "expected", F32);
+    count(expected, "expected", C);
+    for (const Tensor* t : {&Diag, &xs_in, (const Tensor*)&expected}) same_device(Sigma, *t, "every tensor");
+    RLS_GUARD(Sigma);
+    ok(rls_mimo_local_search((const float*)p(Sigma), (const float*)p(Diag), n, (const uint64_t*)p(xs_in), C_in, (uint64_t*)p(xs_out), C, num_ls,
+                             (float*)p(expected), cur_stream(Sigma)), "rls_mimo_local_search");
+}
 void mcpg_pick_best(const Tensor& expected, const Tensor& xs, int64_t N, int64_t total_mcmc_num, int64_t repeat_times, int64_t num_edges,
                     Tensor best_index, Tensor vs_good, Tensor xs_good) {
     dev(expected, "expected", F32);
@@ -1111,6 +1134,7 @@ TORCH_LIBRARY(rlsolver_hip, m) {
           "int seed, Tensor clause_ptr, Tensor lit, Tensor? weight, Tensor(b!) expected, int chain_offset=0, int chain_period=0, int chain_skip=0) -> ()");
     m.def("cheeger_local_search(int graph, Tensor xs_in, int C_in, Tensor(a!) xs_out, int C, Tensor visit_stream, int normalized, int num_ls, "
           "float edge_weight_sum, Tensor(b!) h, Tensor(c!)? cut=None, Tensor(d!)? size=None) -> ()");
+    m.def("mimo_local_search(Tensor Sigma, Tensor Diag, Tensor xs_in, int C_in, Tensor(a!)? xs_out, int C, int num_ls, Tensor(b!) expected) -> ()");
     m.def("maxcut_edge_local_search(int graph, Tensor edge_weights, Tensor xs_in, int C_in, Tensor(a!) xs_out, int C, Tensor visit_stream, "
           "int max_abs_degree, int weight_abs_sum, int gauge_node, int num_ls, Tensor? uniforms, int seed, Tensor(b!) expected, "
           "int chain_offset=0, int chain_period=0, int chain_skip=0) -> ()");
@@ -1174,6 +1198,7 @@ TORCH_LIBRARY_IMPL(rlsolver_hip, CUDA, m) {   // "CUDA" is the HIP dispatch key 
     m.impl("isco_mis_step", &isco_mis_step);
     m.impl("maxsat_local_search", &maxsat_local_search);
     m.impl("cheeger_local_search", &cheeger_local_search);
+    m.impl("mimo_local_search", &mimo_local_search);
     m.impl("maxcut_edge_local_search", &maxcut_edge_local_search);
     m.impl("isco_tsp_step", &isco_tsp_step);
 }

@@ -647,14 +647,15 @@ class MCPGRound(Sharded):
 
 def run_mcpg(data, xs_init: TEN, vs_init: TEN, total_mcmc_num: int, repeat_times: int, num_ls: int, num_rounds: int,
              sample_epoch_num: int = 8, lr: float = 8e-2, log=print, kept_offset: int = 0, total_kept: Optional[int] = None,
-             group=None, seed: Optional[int] = None):
+             group=None, seed: Optional[int] = None, return_round: bool = False):
     """The sampling loop of mcpg() (methods/MCPG.py:353-413) on MCPGRound, with the reference's per-round prints
     ("value ... entropy ..." and "num_samples_per_second: ..." as defined at :405-411: kept chains per round divided
     by the wall time of metro + sampler + merge).  ``xs_init`` [N, M] / ``vs_init`` [M]: the incumbents the reference
     gets from LocalSearch (:337-346).  The policy is the reference's parameter vector through a sigmoid (Simpler,
     :62-73) trained with Adam: dense torch, out of the hot path.  Returns (best value, best x bool [N], samples/s list).
     ``kept_offset`` / ``total_kept`` / ``group``: this process runs a shard of the kept chains (see MCPGRound); value, best x
-    and the policy are those of the whole batch on every rank."""
+    and the policy are those of the whole batch on every rank.  ``return_round``: the MCPGRound comes back as a fourth value (its
+    now_max_res / now_max_info are what the MIMO driver votes over, MCPG.py:184-192)."""
     import time
     device = data.device if hasattr(data, "device") else data.graph.device      # (a MaxCut graph / a Data_MaxSAT)
     rnd = MCPGRound(data, xs_init, vs_init, total_mcmc_num, repeat_times, num_ls, kept_offset=kept_offset,
@@ -683,4 +684,4 @@ def run_mcpg(data, xs_init: TEN, vs_init: TEN, total_mcmc_num: int, repeat_times
             opt.step()
         xs_prob = torch.sigmoid(lin).detach()
     v, x = rnd.best_solution()
-    return v, x, rates
+    return (v, x, rates, rnd) if return_round else (v, x, rates)

@@ -284,6 +284,57 @@ def mcpg_maxcut_edge_local_search(g: DeviceGraph, edge_weights: TEN, xs_in: Pack
     return xs_out, expected
 
 
+def mimo_launch_form(n: int, num_chains: int):
+    """(supported, form) of rls_mimo_local_search_supported: whether n variables fit the kernel's LDS budget at this many chains and
+    which launch form the shape gets (0: 32-chain workgroups of 8 waves, 1: of 4 waves, 2: 64-chain workgroups).  A host query."""
+    import ctypes
+    from . import _abi
+    form = ctypes.c_int32(-1)
+    ok = _abi.lib().rls_mimo_local_search_supported(int(n), int(num_chains), ctypes.byref(form))
+    return bool(ok), int(form.value)
+
+
+def mcpg_mimo_local_search(Sigma: TEN, Diag: TEN, xs_in: PackedChains, num_ls: int, out=None, num_chains: Optional[int] = None,
+                           _score_only: bool = False):
+    """The coordinate search and the value of the MIMO detection sampler (include/rlsolver_hip.h: rls_mimo_local_search).
+    ``Sigma`` f32 [n, n], ``Diag`` f32 [n]; ``xs_in``: PackedChains over the variables (bit 1 = +; may hold fewer chains than
+    ``num_chains``, a multiple of 64: broadcast).  ``out``: a PackedChains to write (may be xs_in itself) or None = node-major f32
+    holding 0|1 (the packed result through the unpack kernel).  ``num_ls`` >= 1: every variable counts +-2 until its first visit.
+    Returns (xs_out, expected f32 [C]) with expected = info^T Sigma info + Diag . info, the quantity the sampler minimises."""
+    if not isinstance(xs_in, PackedChains):
+        raise TypeError("xs_in must be a PackedChains")
+    _check(Sigma, "Sigma", (torch.float32,))
+    dev = Sigma.device
+    if Sigma.dim() != 2 or Sigma.shape[0] != Sigma.shape[1] or Sigma.shape[0] < 1:
+        raise ValueError(f"Sigma must be square [n, n], got {tuple(Sigma.shape)}")
+    n = Sigma.shape[0]
+    _check(Diag, "Diag", (torch.float32,), dev, (n,))
+    if xs_in.device != dev or xs_in.num_nodes != n:
+        raise ValueError(f"xs_in must hold {n} variables on {dev}")
+    Cc = xs_in.num_chains if num_chains is None else int(num_chains)
+    if not _score_only and int(num_ls) < 1:
+        raise ValueError(f"num_ls must be >= 1 (a sweep-less call would leave +-2 entries), got {num_ls}")
+    if Cc != xs_in.num_chains and (xs_in.num_chains % 64 != 0 or xs_in.num_chains > Cc):
+        raise ValueError("a broadcast input needs a multiple of 64 chains, fewer than num_chains")
+    ok, _ = mimo_launch_form(n, Cc)
+    if not ok:
+        raise ValueError(f"n={n} is beyond the LDS limit of the MIMO kernel at {Cc} chains (rls_mimo_local_search_supported)")
+    expected = torch.empty(Cc, dtype=torch.float32, device=dev)
+    if _score_only:                      # Data_MIMO.result: the value of +-1 chains, no sweep, nothing written
+        _t.mimo_local_search(Sigma, Diag, xs_in.words, xs_in.num_chains, None, Cc, 0, expected)
+        return xs_in, expected
+    if out is None:
+        packed = PackedChains.empty(n, Cc, dev)
+    else:
+        if not isinstance(out, PackedChains) or out.num_chains != Cc or out.num_nodes != n or out.device != dev:
+            raise ValueError("out must be a PackedChains of num_chains chains")
+        if out.words.data_ptr() == xs_in.words.data_ptr() and xs_in.num_chains != Cc:
+            raise ValueError("in-place needs xs_in to hold num_chains chains")
+        packed = out
+    _t.mimo_local_search(Sigma, Diag, xs_in.words, xs_in.num_chains, packed.words, Cc, int(num_ls), expected)
+    return (packed.unpack() if out is None else packed), expected
+
+
 def mcpg_pick_best(expected: TEN, xs, total_mcmc_num: int, repeat_times: int, num_edges: int):
     """K8 second half.  Returns (best_index int64 [M], vs_good f32 [M], xs_good: f32 [N, M] or PackedChains of M chains)."""
     st, sb, N, Cc = _chains(xs, "xs")

@@ -1942,7 +1942,97 @@ def gen_maxcut_edge():
     save("maxcut_edge", **out)
 
 
-ALL = {"graph_forms": gen_graph_forms, "cheeger": gen_cheeger, "maxcut_edge": gen_maxcut_edge, "maxsat": gen_maxsat, "mcpg_weighted": gen_mcpg_weighted, "isco_steps": gen_isco_steps, "isco_mis": gen_isco_mis, "spinsystem_cpu": gen_spinsystem_cpu, "spinsystem": gen_spinsystem, "spinsystem_perenv": gen_spinsystem_perenv, "qubo": gen_qubo, "qubo_asym": gen_qubo_asym, "isco_maxcut": gen_isco_maxcut, "maxcut": gen_maxcut, "sweep": gen_sweep, "lsclass": gen_local_search_class, "ppo": gen_ppo,
+def gen_mimo():
+    """mcpg_sampling_mimo (rlsolver/methods/MCPG/sampling.py:288-320) run on CPU, every draw of the walk recorded, on two instances of
+    n = 24 variables (K = N = 12) from this package's seeded generator (the reference ships no MIMO data): one integer-valued
+    (noise factor 1: Sigma, Diag, sca are integers, every float32 sum exact) and one real-valued at SNR 8.  The reference's loaders
+    leave Sigma / Diag in float64 and its sampler then raises on the float32 chains: the data are cast to float32, the only way it
+    runs.  The same seed precedes the num_ls = 1 and the num_ls = 3 call: both see the same walk, stored once.  For the real
+    instance no decision of either run may come closer to its threshold than the float32 bound of tests/mimo_oracle.py (the seed is
+    chosen so), which makes the recorded chains the unambiguous answer.
+    + what the reference's own read_data_mimo3 / read_data_mimo5 return for a small instance (K = 3, N = 4) written in both file forms."""
+    import tempfile
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    sys.path.insert(0, os.path.join(root, "tests"))
+    try:
+        from rlsolver_amd.methods import MCPG_mimo as mm
+        import mimo_oracle as orc
+    finally:
+        sys.path.remove(root)
+        sys.path.remove(os.path.join(root, "tests"))
+    smp = _load_mcpg_sampling()
+    dl = _load_upstream_mcpg("dataloader")
+    cpu = th.device("cpu")
+    bits = lambda t: np.packbits(u8(t), axis=0)      # noqa: E731
+    out, cases = {}, []
+    M, R = 6, 4
+    C = M * R
+    for ii, (name, integer, seed) in enumerate((("int_24", True, 4101), ("real_24", False, 4202))):
+        inst = mm.mimo_instance(12, 12, 8, seed, integer=integer)
+        Sigma, Diag, X, sca, noise = mm.instance_arrays(inst["H"], inst["X"], inst["v"], inst["K"], inst["SNR"], 1.0 if integer else None)
+        n = Sigma.shape[0]
+        data = [th.tensor(Sigma).float(), th.tensor(Diag).float(), th.tensor(X), th.tensor(sca), noise]
+        if integer:
+            assert np.array_equal(Sigma, np.round(Sigma)) and np.array_equal(Diag, np.round(Diag)) and sca == round(sca)
+            assert 2 * np.abs(Sigma).sum(axis=1).max() + np.abs(Diag).max() < 2 ** 24 and np.abs(Sigma).sum() + np.abs(Diag).sum() + abs(sca) < 2 ** 24
+        g = th.Generator().manual_seed(6100 + ii)
+        probs = th.rand(n, generator=g) * 0.6 + 0.2
+        start = th.randint(0, 2, (n, C), generator=g).float()
+        change_times = max(1, n // 10)
+        out[f"{name}/n"], out[f"{name}/M"], out[f"{name}/R"] = np.int64(n), np.int64(M), np.int64(R)
+        out[f"{name}/Sigma"], out[f"{name}/Diag"] = data[0].numpy().copy(), data[1].numpy().copy()
+        out[f"{name}/X"], out[f"{name}/sca"], out[f"{name}/noise"] = X.copy(), np.float64(sca), np.float64(noise)
+        out[f"{name}/probs"], out[f"{name}/start"], out[f"{name}/change_times"] = probs.numpy().copy(), bits(start), np.int64(change_times)
+        walk = None
+        for num_ls in (1, 3):
+            th.manual_seed(6200 + ii)
+            with Recorder("rand", "randint") as rec:
+                max_res, best, raw, value = smp.mcpg_sampling_mimo(data, start.clone(), probs, num_ls, change_times, M, device=cpu)
+            index = th.stack(rec.log["randint"]).numpy().astype(np.int16)
+            u = th.stack(rec.log["rand"]).numpy().copy()
+            if walk is None:
+                walk = (index, u, u8(raw))
+                out[f"{name}/index"], out[f"{name}/u"], out[f"{name}/raw"] = index, u, bits(raw)
+            else:
+                assert np.array_equal(walk[0], index) and np.array_equal(walk[1], u) and np.array_equal(walk[2], u8(raw))
+            assert max_res.dtype == th.float32 and value.dtype == th.float32
+            o = orc.sampler(out[f"{name}/Sigma"], out[f"{name}/Diag"], sca, u8(raw), num_ls, M)
+            if not integer:
+                assert o["safe"].all(), f"{name} ls{num_ls}: a decision within the float32 bound of its threshold -- pick another seed"
+            assert np.array_equal(o["best"], u8(best)), f"{name} ls{num_ls}: the oracle disagrees with the reference"
+            case = f"{name}/ls{num_ls}"
+            cases.append(case)
+            out[f"{case}/max_res"], out[f"{case}/best"], out[f"{case}/value"] = max_res.numpy().copy(), bits(best), value.numpy().copy()
+    # the loaders, on files of both forms
+    inst = mm.mimo_instance(3, 4, 6, 4303)
+    with tempfile.TemporaryDirectory() as tmp:
+        txt = os.path.join(tmp, "inst.txt")
+        mm.write_mimo3(txt, inst)
+        out["loader/text"] = np.array(open(txt).read())
+        d3 = dl.read_data_mimo3(txt, 10, 0, device=cpu)
+        os.makedirs(os.path.join(tmp, "data", "MIMO", "4QAM4_3"))
+        mm.write_mimo5(os.path.join(tmp, "data", "MIMO", "4QAM4_3", "4QAM3_2.npz"), inst)
+        saved, dl.rlsolver_path = dl.rlsolver_path, tmp
+        try:
+            d5 = dl.read_data_mimo5(3, 4, 6, 10, 17, device=cpu)          # 17 // 10 + 1 = file 2
+        finally:
+            dl.rlsolver_path = saved
+    for k in ("K", "SNR", "H", "X", "v"):
+        out[f"loader/inst/{k}"] = np.asarray(inst[k])
+    out["loader/mimo5_args"] = np.array([3, 4, 6, 10, 17], dtype=np.int64)
+    for tag, d in (("mimo3", d3), ("mimo5", d5)):
+        # (read_data_mimo3 passes H through float32 torch tensors: its Sigma is a float32 product; read_data_mimo5 stays in float64)
+        out[f"loader/{tag}/Sigma"], out[f"loader/{tag}/Diag"], out[f"loader/{tag}/X"] = d[0].numpy().copy(), d[1].numpy().copy(), d[2].numpy().copy()
+        out[f"loader/{tag}/sca"], out[f"loader/{tag}/noise"] = np.float64(d[3].item()), np.float64(d[4])
+    out["cases"] = np.array(cases)
+    out["source"] = np.array("recorded from the reference's mcpg_sampling_mimo on CPU (Sigma / Diag cast to float32) on instances of "
+                             "rlsolver_amd.methods.MCPG_mimo.mimo_instance, and from its read_data_mimo3 / read_data_mimo5 (float64, as they "
+                             "return it); start / raw / best as np.packbits(axis=0) of the [n, C] 0|1 arrays")
+    save("mimo", **out)
+
+
+ALL = {"graph_forms": gen_graph_forms, "mimo": gen_mimo, "cheeger": gen_cheeger, "maxcut_edge": gen_maxcut_edge, "maxsat": gen_maxsat, "mcpg_weighted": gen_mcpg_weighted, "isco_steps": gen_isco_steps, "isco_mis": gen_isco_mis, "spinsystem_cpu": gen_spinsystem_cpu, "spinsystem": gen_spinsystem, "spinsystem_perenv": gen_spinsystem_perenv, "qubo": gen_qubo, "qubo_asym": gen_qubo_asym, "isco_maxcut": gen_isco_maxcut, "maxcut": gen_maxcut, "sweep": gen_sweep, "lsclass": gen_local_search_class, "ppo": gen_ppo,
        "select": gen_select, "mcpg": gen_mcpg, "tsp": gen_tsp, "tsp_2opt": gen_tsp_2opt, "encoder": gen_encoder,
        "wgain": gen_weighted_gain, "mcpg_glue": gen_mcpg_glue, "evaluator": gen_evaluator, "spinsystem_options": gen_spinsystem_options,
        "api_surface": gen_api_surface, "mcpg_data": gen_mcpg_data,
