@@ -973,6 +973,37 @@ int rls_isco_mis_step(const rls_graph* g, const float* x, float* y_out, int64_t 
                       int64_t env_offset, float* energy_out, float* acc_out, float* terms_out, uint8_t* mask_out,
                       void* scratch, int64_t scratch_bytes, void* stream);
 
+/* PISCO_maxcut.tensor_core_energy's product  envs/env_ISCO.py:436-444 (XA = matmul(delta_x, adj_matrix), :439) on the f16 matrix
+ * instruction (f16 operands, f32 accumulate):  r_out f32 [B, Np] = delta(x) . A,  delta_k = x_k > 0 ? +1 : -1.
+ * adj = A, IEEE binary16 [Np, Np] row-major (the reference's adj_matrix: zero-padded from n to Np = ceil(n / 8) * 8 nodes,
+ * methods/ISCO/util_maxcut.py:17-35); x binary16 [B, Np]; both 16-byte aligned, Np a positive multiple of 8.  Padded columns of
+ * x count (x = 0 is delta = -1): the zero rows of A silence them.  A need not be symmetric here.  The result is not rounded to
+ * f16; it is exact while every |sum| stays below 2^24 on integer-valued A. */
+int rls_pisco_product(const uint16_t* adj, int64_t Np, const uint16_t* x, int64_t B, float* r_out, void* stream);
+
+/* Bytes of scratch rls_pisco_step needs: r f32 [B, Np] followed by ord int32 [B, Np] = 8 B Np (0 for B <= 0 or an Np that is no
+ * positive multiple of 8).  Host query, nothing is launched. */
+int64_t rls_pisco_scratch_bytes(int64_t Np, int64_t B);
+
+/* PISCO_maxcut.step(x, path_length, temperature)  envs/env_ISCO.py:384-434 (get_local_dist :407-416, tensor_core_energy :436-444,
+ * proposal :394-405, ll_y2x :418-430; multinomial methods/ISCO/util.py:19-60): rls_pisco_product, then ONE kernel that is
+ * rls_isco_maxcut_step with the local distribution of a sample read from its row of r:
+ *   ll_x = -0.25 * sum_k r_k delta_k / T;  log_prob = log_softmax(delta_k r_k / 2T) over all Np columns (a padded column scores 0
+ *   and can be selected and flipped, as in the reference);
+ *   the proposal's row is r'_j = r_j - 2 sum_{k selected} delta_k A[k][j] -- A must be SYMMETRIC (the closed-form gradient and
+ *   this update both assume it; the reference builds A from an undirected graph).
+ * half_rounding != 0 (the reference's arithmetic): r, r' and sum_k r_k delta_k are each rounded to binary16 once before use;
+ * 0: everything stays f32.  x, y_out binary16 [B, Np] holding 0|1 (x > 0 reads as 1); y_out must not alias x.  path_length,
+ * temperature, the two draws (both or neither; generator keyed by (seed, env_offset + b, column)), energy_out / acc_out /
+ * terms_out / mask_out (uint8 [B, Np]): as rls_isco_maxcut_step.  scratch: rls_pisco_scratch_bytes(Np, B) bytes, 16-byte aligned,
+ * clobbered.  Checks, all before the first launch and in this order: Np % 8, B (0 is a no-op), temperature > 0, Np past the
+ * rows-in-LDS limit (~16 000 columns: RLS_EUNSUPPORTED with the byte counts; there is no rows-in-scratch form), then the pointers,
+ * aliasing and scratch_bytes.  RLS_ISCO_FORCE_WG / RLS_ISCO_SEL_CAP act as for the other steps. */
+int rls_pisco_step(const uint16_t* adj, int64_t Np, const uint16_t* x, uint16_t* y_out, int64_t B, const int64_t* path_length,
+                   float temperature, int32_t half_rounding, const float* u_gumbel, const float* u_accept, uint64_t seed,
+                   int64_t env_offset, float* energy_out, float* acc_out, float* terms_out, uint8_t* mask_out, void* scratch,
+                   int64_t scratch_bytes, void* stream);
+
 /* ISCO_TSP.step(x, path_length, temperature)  envs/env_ISCO.py:188-236 in ONE kernel (one wave per env, the tour,
  * its inverse and -- when it fits -- the distance matrix in LDS): path_length times { opt_2 (:238-335: partner
  * city per position from the nearest / random tables, swap delta, ban mask) -> logits = -delta / 2T (banned:

@@ -139,6 +139,8 @@ SIGNATURES = {
     "rls_isco_mis_step": [_G, _P, _P, _I64, _P, _F32, _F32, _P, _P, _U64, _I64, _P, _P, _P, _P, _P, _I64, _P],
     "rls_isco_tsp_step": [_P, _I64, _P, C.c_int32, _F32, _P, C.c_int32, _P, _P, _I64, C.c_int32, _F32, _P, _P, _P, _P, _P, _U64, _I64,
                           _P, _P, _P, _P],
+    "rls_pisco_product": [_P, _I64, _P, _I64, _P, _P],
+    "rls_pisco_step": [_P, _I64, _P, _P, _I64, _P, _F32, C.c_int32, _P, _P, _U64, _I64, _P, _P, _P, _P, _P, _I64, _P],
     "rls_copy_rows": [_P, _P, _I64, _P, _P, _I64, _P],
     "rls_best_update": [_P, _P, _INT, _I64, _I64, _INT, _P, _P, _P, _P, _I64, _INT, _P],
     "rls_best_key": [_P, _INT, _I64, C.c_int32, _I64, _I64, _P, _P, _P, _P],
@@ -167,6 +169,7 @@ PLAIN = {"rls_version": ([], _INT), "rls_device_count": ([], _INT), "rls_last_er
          "rls_mcpg_metro_scratch_bytes": ([_I64, _I64], _I64),
          "rls_tsp_tables8_bytes": ([_I64, C.c_int32], _I64),
          "rls_isco_maxcut_scratch_bytes": ([_G, _I64], _I64),
+         "rls_pisco_scratch_bytes": ([_I64, _I64], _I64),
          "rls_maxcut_ls_scratch_bytes": ([_G, _I64, C.c_int32, C.c_int32], _I64),
          "rls_maxcut_ls_slices": ([_G, _I64, C.c_int32], _INT)}
 

@@ -79,8 +79,9 @@ __device__ __forceinline__ float noreplacement_ll_sum(int count, float base, int
 
 // Order of a selection that does not fit the LDS list (count > capacity: path lengths in the thousands on a graph whose
 // rows nearly fill LDS -- the reference draws Poisson(~10) path lengths, main_ISCO_maxcut.py:22-30): repeated extraction of
-// the maximum, O(count N / 64) per sample, ONE wave.  The node ids leave in order into `ord` -- global scratch, the sample's
-// own row of y_out reinterpreted (written last by the step) -- `taken` is N bytes of LDS that are free at this point (yb).
+// the maximum, O(count N / 64) per sample, ONE wave.  The node ids leave in order into `ord` -- global scratch: for the graph
+// models the sample's own f32 row of y_out reinterpreted (written last by the step), for the dense step (f16 rows: too short) a
+// row of the caller's scratch -- `taken` is N bytes of LDS that are free at this point (yb).
 // Equal keys: lowest node first.
 __device__ __noinline__ void isco_order_by_extraction(const float* pert, uint8_t* taken, int64_t N, uint32_t prefix, int count,
                                                       int32_t* ord, int lane) {
@@ -618,6 +619,384 @@ __global__ __launch_bounds__(kIscoWgWaves * kWave) void k_isco_maxcut_step_wg(Is
     for (int64_t i = tid; i < N; i += NT) yo[i] = (float)(accept ? yb[i] : xb[i]);
 }
 
+// ----------------------------------------------------------------------------------------------- PISCO (dense, weighted MaxCut)
+// PISCO_maxcut.step (env_ISCO.py:384-434): the MaxCut step with the local distribution of a sample read from its row of the
+// dense product r = delta . A (rls_pisco_product, rls_pisco.hip) instead of from neighbour walks:
+//   score_k = delta_k r_k / (2T),  energy = -0.25 sum_k r_k delta_k / T   (tensor_core_energy :436-444 and its autograd)
+// The proposal's row is the rank-L update r'_j = r_j - 2 sum_{k selected} delta_k A[k][j] (delta of x; contiguous f16 rows of the
+// symmetric A), so a step runs one product.  half_rounding: r and sum_k r_k delta_k each rounded to f16 once, as the reference's
+// half matmul and half sum do.  Samples are f16 in and out; all Np columns -- the padded ones too -- take part.
+// These kernels are copies of the two above, not further instantiations of them: the graph models keep their code as it was.
+struct PiscoArgs {
+    const uint16_t* adj; int64_t N;                       // f16 [N, N], N % 8 == 0
+    const uint16_t* x; uint16_t* y_out; int64_t B;        // f16 [B, N]
+    const int64_t* path_length; float temperature; int half_rounding;
+    const float* u_gumbel; const float* u_accept; uint64_t seed; int64_t env_offset;
+    float* energy_out; float* acc_out; float* terms_out; uint8_t* mask_out;
+    int P;
+    const float* r;                                       // f32 [B, N] from rls_pisco_product
+    int32_t* ord;                                         // int32 [B, N]: the order of a selection larger than the list
+};
+
+__device__ __forceinline__ bool pisco_is_set(uint16_t h) { return __builtin_bit_cast(_Float16, h) > (_Float16)0; }
+__device__ __forceinline__ float pisco_round_f16(float v) { return (float)(_Float16)v; }
+// torch.clamp(v, max=0): a NaN stays a NaN (the f16 sum of a large instance overflows to -inf in the reference; -inf - -inf then
+// rejects the proposal there, where fminf would return 0 and accept it)
+__device__ __forceinline__ float pisco_clamp0(float v) { return v != v ? v : fminf(v, 0.0f); }
+__device__ __forceinline__ float pisco_energy(float s, float temperature, bool half) {
+    return (-0.25f * (half ? pisco_round_f16(s) : s)) / temperature;
+}
+// one column: the score into lp[i], the column's term of sum_k r_k delta_k returned
+__device__ __forceinline__ float pisco_score(const uint8_t* s, const float* rrow, float* lp, int64_t i, float temperature, bool half,
+                                             float& mx) {
+    const float d = s[i] ? 1.0f : -1.0f;
+    const float rv = half ? pisco_round_f16(rrow[i]) : rrow[i];
+    const float sc = (d * rv) / (2.0f * temperature);
+    lp[i] = sc;
+    mx = fmaxf(mx, sc);
+    return rv * d;
+}
+
+// r'[8c .. 8c + 7] = r[8c ..] - 2 sum_k delta_k A[sel_k][8c ..] in list order, for the 8-column pieces c = t, t + nt, ...
+template <typename S>
+__device__ __forceinline__ void pisco_rank_update(const PiscoArgs& a, const float* rrow, float* rnew, const uint8_t* xb, int count,
+                                                  S sel_at, int t, int nt) {
+    const int64_t N = a.N;
+    for (int64_t c = t; c < (N >> 3); c += nt) {
+        float v[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = rrow[c * 8 + e];
+        for (int k = 0; k < count; ++k) {
+            const int node = sel_at(k);
+            const float two_d = xb[node] ? 2.0f : -2.0f;
+            const u32x4 row = *reinterpret_cast<const u32x4*>(a.adj + (int64_t)node * N + c * 8);
+            const uint32_t wd[4] = {row.x, row.y, row.z, row.w};
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+                v[e] -= two_d * (float)__builtin_bit_cast(_Float16, (uint16_t)(wd[e >> 1] >> ((e & 1) * 16)));
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) rnew[c * 8 + e] = v[e];
+    }
+}
+
+__device__ __forceinline__ float pisco_local_dist(const uint8_t* s, const float* rrow, float* lp, int64_t N, float temperature,
+                                                  bool half, int lane) {
+    float sum = 0.0f, mx = -INFINITY;
+    for (int64_t i = lane; i < N; i += kWave) sum += pisco_score(s, rrow, lp, i, temperature, half, mx);
+    mx = wave_max_f(mx);
+    float se = 0.0f;
+    for (int64_t i = lane; i < N; i += kWave) se += expf(lp[i] - mx);
+    const float lse = logf(wave_sum_f32x(se));
+    for (int64_t i = lane; i < N; i += kWave) lp[i] = (lp[i] - mx) - lse;
+    lds_fence();
+    return pisco_energy(wave_sum_f32x(sum), temperature, half);
+}
+
+__global__ __launch_bounds__(512) void k_pisco_step(PiscoArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wib = threadIdx.x / kWave;
+    const int64_t b = (int64_t)blockIdx.x * (blockDim.x / kWave) + wib;
+    if (b >= a.B) return;
+    const int64_t N = a.N;
+    const int P = a.P;
+    const size_t per_wave = 2 * (size_t)N + (size_t)N * 8 + (size_t)P * 8;
+    unsigned char* base = smem + (size_t)wib * per_wave;
+    uint8_t* xb = base;
+    uint8_t* yb = base + N;
+    float* lp = reinterpret_cast<float*>(base + 2 * N);
+    float* pert = lp + N;
+    float* skey = pert + N;
+    int32_t* sidx = reinterpret_cast<int32_t*>(skey + P);
+    const uint16_t* xr = a.x + b * N;
+    const float* rrow = a.r + b * N;
+    const float T = a.temperature;
+    const bool half = a.half_rounding != 0;
+    const uint64_t genv = (uint64_t)(b + a.env_offset);
+
+    for (int64_t i = lane; i < N; i += kWave) xb[i] = pisco_is_set(xr[i]) ? 1 : 0;
+    lds_fence();
+    // ---- forward: ll_x, proposal distribution, Gumbel perturbation (env_ISCO.py:407-416, util.py:498-516)
+    const float ll_x = pisco_local_dist(xb, rrow, lp, N, T, half, lane);
+    float lmax = -INFINITY;
+    for (int64_t i = lane; i < N; i += kWave) {
+        const float u = a.u_gumbel ? a.u_gumbel[b * N + i] : isco_unit(isco_draw(a.seed, genv, (uint32_t)i, 0, 1));
+        const float l = lp[i];
+        pert[i] = l - logf(-logf(u));
+        lmax = fmaxf(lmax, l);
+    }
+    lmax = wave_max_f(lmax);
+    lds_fence();
+    // ---- threshold = L-th largest perturbed value: radix select on the monotone key
+    int64_t L = a.path_length[b];
+    L = L < 1 ? 1 : (L > N ? N : L);
+    uint32_t prefix = 0;
+    int want = (int)L;
+    if (N <= 32 * kWave) {
+        uint32_t kk[32];
+#pragma unroll
+        for (int j = 0; j < 32; ++j) {
+            const int64_t i = lane + (int64_t)j * kWave;
+            kk[j] = i < N ? fkey(pert[i]) : 0u;
+        }
+        for (int bit = 31; bit >= 0; --bit) {
+            const uint32_t hi_mask = bit == 31 ? 0u : (0xFFFFFFFFu << (bit + 1));
+            int cnt = 0;
+#pragma unroll
+            for (int j = 0; j < 32; ++j) cnt += ((kk[j] & hi_mask) == prefix) && ((kk[j] >> bit) & 1u);
+            cnt = wave_sum_i32(cnt);
+            if (cnt >= want) prefix |= 1u << bit;
+            else want -= cnt;
+        }
+    } else {
+        for (int bit = 31; bit >= 0; --bit) {
+            const uint32_t hi_mask = bit == 31 ? 0u : (0xFFFFFFFFu << (bit + 1));
+            int cnt = 0;
+            for (int64_t i = lane; i < N; i += kWave) {
+                const uint32_t k = fkey(pert[i]);
+                cnt += ((k & hi_mask) == prefix) && ((k >> bit) & 1u);
+            }
+            cnt = wave_sum_i32(cnt);
+            if (cnt >= want) prefix |= 1u << bit;
+            else want -= cnt;
+        }
+    }
+    // ---- selected set, compacted then sorted by perturbed value, descending
+    int count = 0;
+    for (int64_t i0 = 0; i0 < N; i0 += kWave) {
+        const int64_t i = i0 + lane;
+        const bool sel = i < N && fkey(pert[i]) >= prefix;
+        const uint64_t m = ballot64(sel);
+        if (sel) {
+            const int at = count + __popcll(m & ((1ull << lane) - 1ull));
+            if (at < P) {
+                skey[at] = pert[i];
+                sidx[at] = (int)i;
+            }
+        }
+        count += __popcll(m);
+    }
+    const bool big = count > P;
+    int32_t* ord = a.ord + b * N;                                // an f16 output row is too short for it: the caller's scratch
+    if (big) {
+        isco_order_by_extraction(pert, yb, N, prefix, count, ord, lane);
+    } else {
+        int P2 = 1;
+        while (P2 < count) P2 <<= 1;
+        for (int k = count + lane; k < P2; k += kWave) { skey[k] = -INFINITY; sidx[k] = -1; }
+        lds_fence();
+        for (int size = 2; size <= P2; size <<= 1) {
+            for (int stride = size >> 1; stride >= 1; stride >>= 1) {
+                for (int t = lane; t < (P2 >> 1); t += kWave) {
+                    const int lo = ((t / stride) * (stride << 1)) + (t % stride);
+                    const int hi = lo + stride;
+                    const bool desc = ((lo & size) == 0);
+                    const float k0 = skey[lo], k1 = skey[hi];
+                    const int i0 = sidx[lo], i1 = sidx[hi];
+                    const bool lt = (k0 < k1) || (k0 == k1 && i0 > i1);      // equal keys: lowest node first, as the extraction
+                    if (lt == desc) {
+                        skey[lo] = k1; skey[hi] = k0;
+                        sidx[lo] = i1; sidx[hi] = i0;
+                    }
+                }
+                lds_fence();
+            }
+        }
+    }
+    auto sel_at = [&](int k) -> int { return big ? ord[k] : sidx[k]; };
+    const float ll_x2y = noreplacement_ll_sum(count, lmax, lane, [&](int k) { return lp[sel_at(k)]; });
+    // ---- y = x with the selected columns flipped; its row of the product by the rank-L update, into pert (free from here on)
+    for (int64_t i = lane; i < N; i += kWave) yb[i] = xb[i];
+    lds_fence();
+    for (int k = lane; k < count; k += kWave) yb[sel_at(k)] ^= 1;
+    pisco_rank_update(a, rrow, pert, xb, count, sel_at, lane, kWave);
+    lds_fence();
+    if (a.mask_out) {
+        for (int64_t i = lane; i < N; i += kWave) a.mask_out[b * N + i] = xb[i] ^ yb[i];
+    }
+    // ---- backward
+    const float ll_y = pisco_local_dist(yb, pert, lp, N, T, half, lane);
+    float bmax = -INFINITY;
+    for (int k = lane; k < count; k += kWave) bmax = fmaxf(bmax, lp[sel_at(k)]);
+    bmax = wave_max_f(bmax);
+    const float ll_y2x = noreplacement_ll_sum(count, bmax, lane, [&](int k) { return lp[sel_at(count - 1 - k)]; });
+    const float log_acc = pisco_clamp0(((ll_y + ll_y2x) - ll_x) - ll_x2y);
+    const float ua = a.u_accept ? a.u_accept[b] : isco_unit(isco_draw(a.seed, genv, 0xFFFFFFFFu, 0, 2));
+    const bool accept = logf(ua + 1e-24f) < log_acc;
+    uint16_t* yo = a.y_out + b * N;
+    for (int64_t i = lane; i < N; i += kWave) yo[i] = (accept ? yb[i] : xb[i]) ? 0x3C00 : 0;
+    if (lane == 0) {
+        if (a.energy_out) a.energy_out[b] = ll_y * T;
+        if (a.acc_out) a.acc_out[b] = expf(log_acc);
+        if (a.terms_out) {
+            float* t = a.terms_out + b * 5;
+            t[0] = ll_x; t[1] = ll_x2y; t[2] = ll_y; t[3] = ll_y2x; t[4] = log_acc;
+        }
+    }
+}
+
+__device__ __forceinline__ float pisco_local_dist_wg(const uint8_t* s, const float* rrow, float* lp, int64_t N, float temperature,
+                                                     bool half, IscoWgScratch* sc, int lane, int w, int tid) {
+    constexpr int NT = kIscoWgWaves * kWave;
+    float sum = 0.0f, mx = -INFINITY;
+    for (int64_t i = tid; i < N; i += NT) sum += pisco_score(s, rrow, lp, i, temperature, half, mx);
+    mx = isco_block_max(mx, sc, lane, w);
+    float se = 0.0f;
+    for (int64_t i = tid; i < N; i += NT) se += expf(lp[i] - mx);
+    const float lse = logf(isco_block_sum(se, sc, lane, w));
+    for (int64_t i = tid; i < N; i += NT) lp[i] = (lp[i] - mx) - lse;
+    return pisco_energy(isco_block_sum(sum, sc, lane, w), temperature, half);      // (its barriers also publish lp[])
+}
+
+__global__ __launch_bounds__(kIscoWgWaves * kWave) void k_pisco_step_wg(PiscoArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
+    const int tid = threadIdx.x, NT = kIscoWgWaves * kWave;
+    const int64_t b = blockIdx.x;
+    const int64_t N = a.N;
+    const int P = a.P;
+    uint8_t* xb = smem;
+    uint8_t* yb = smem + N;
+    float* lp = reinterpret_cast<float*>(smem + 2 * N);
+    float* pert = lp + N;
+    float* skey = pert + N;
+    int32_t* sidx = reinterpret_cast<int32_t*>(skey + P);
+    IscoWgScratch* sc = reinterpret_cast<IscoWgScratch*>(sidx + P);
+    const uint16_t* xr = a.x + b * N;
+    const float* rrow = a.r + b * N;
+    const float T = a.temperature;
+    const bool half = a.half_rounding != 0;
+    const uint64_t genv = (uint64_t)(b + a.env_offset);
+
+    for (int64_t i = tid; i < N; i += NT) xb[i] = pisco_is_set(xr[i]) ? 1 : 0;
+    __syncthreads();
+    const float ll_x = pisco_local_dist_wg(xb, rrow, lp, N, T, half, sc, lane, w, tid);
+    float lmax = -INFINITY;
+    for (int64_t i = tid; i < N; i += NT) {
+        const float u = a.u_gumbel ? a.u_gumbel[b * N + i] : isco_unit(isco_draw(a.seed, genv, (uint32_t)i, 0, 1));
+        const float l = lp[i];
+        pert[i] = l - logf(-logf(u));
+        lmax = fmaxf(lmax, l);
+    }
+    lmax = isco_block_max(lmax, sc, lane, w);
+    int64_t L = a.path_length[b];
+    L = L < 1 ? 1 : (L > N ? N : L);
+    uint32_t prefix = 0;
+    int want = (int)L;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        const uint32_t hi_mask = shift == 24 ? 0u : (0xFFFFFFFFu << (shift + 8));
+        for (int k = tid; k < 256; k += NT) sc->hist[k] = 0;
+        __syncthreads();
+        for (int64_t i = tid; i < N; i += NT) {
+            const uint32_t k = fkey(pert[i]);
+            if ((k & hi_mask) == prefix) atomicAdd(&sc->hist[(k >> shift) & 255u], 1);
+        }
+        __syncthreads();
+        if (w == 0) {
+            int c[4], tot = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { c[q] = sc->hist[lane * 4 + q]; tot += c[q]; }
+            int suf = tot;
+#pragma unroll
+            for (int d = 1; d < kWave; d <<= 1) {
+                const int o = __shfl_down(suf, d, 64);
+                if (lane + d < kWave) suf += o;
+            }
+            const int above = suf - tot;
+            int byte_found = -1, want_left = 0, run = above;
+#pragma unroll
+            for (int q = 3; q >= 0; --q) {
+                if (byte_found < 0 && run < want && run + c[q] >= want) { byte_found = lane * 4 + q; want_left = want - run; }
+                run += c[q];
+            }
+            if (byte_found >= 0) { sc->prefix = prefix | ((uint32_t)byte_found << shift); sc->want = want_left; }
+        }
+        __syncthreads();
+        prefix = sc->prefix;
+        want = sc->want;
+    }
+    if (tid == 0) sc->count = 0;
+    __syncthreads();
+    for (int64_t i = tid; i < N; i += NT) {
+        if (fkey(pert[i]) >= prefix) {
+            const int at = atomicAdd(&sc->count, 1);
+            if (at < P) {
+                skey[at] = pert[i];
+                sidx[at] = (int)i;
+            }
+        }
+    }
+    __syncthreads();
+    const int count = sc->count;
+    const bool big = count > P;
+    int32_t* ord = a.ord + b * N;
+    auto sel_at = [&](int k) -> int { return big ? ord[k] : sidx[k]; };
+    float ll_x2y = 0.0f;
+    if (w == 0 && big) {
+        isco_order_by_extraction(pert, yb, N, prefix, count, ord, lane);
+        ll_x2y = noreplacement_ll_sum(count, lmax, lane, [&](int k) { return lp[ord[k]]; });
+    } else if (w == 0) {
+        int P2 = 1;
+        while (P2 < count) P2 <<= 1;
+        for (int k = count + lane; k < P2; k += kWave) { skey[k] = -INFINITY; sidx[k] = -1; }
+        lds_fence();
+        for (int size = 2; size <= P2; size <<= 1) {
+            for (int stride = size >> 1; stride >= 1; stride >>= 1) {
+                for (int t = lane; t < (P2 >> 1); t += kWave) {
+                    const int lo = ((t / stride) * (stride << 1)) + (t % stride);
+                    const int hi = lo + stride;
+                    const bool desc = ((lo & size) == 0);
+                    const float k0 = skey[lo], k1 = skey[hi];
+                    const int i0 = sidx[lo], i1 = sidx[hi];
+                    const bool lt = (k0 < k1) || (k0 == k1 && i0 > i1);
+                    if (lt == desc) {
+                        skey[lo] = k1; skey[hi] = k0;
+                        sidx[lo] = i1; sidx[hi] = i0;
+                    }
+                }
+                lds_fence();
+            }
+        }
+        ll_x2y = noreplacement_ll_sum(count, lmax, lane, [&](int k) { return lp[sidx[k]]; });
+    }
+    // ---- y = x with the selected columns flipped; its row of the product by the rank-L update, into pert (free from here on)
+    __syncthreads();
+    for (int64_t i = tid; i < N; i += NT) yb[i] = xb[i];
+    __syncthreads();
+    for (int k = tid; k < count; k += NT) yb[sel_at(k)] ^= 1;
+    pisco_rank_update(a, rrow, pert, xb, count, sel_at, tid, NT);
+    __syncthreads();
+    if (a.mask_out) {
+        for (int64_t i = tid; i < N; i += NT) a.mask_out[b * N + i] = xb[i] ^ yb[i];
+    }
+    // ---- backward
+    const float ll_y = pisco_local_dist_wg(yb, pert, lp, N, T, half, sc, lane, w, tid);
+    if (w == 0) {
+        float bmax = -INFINITY;
+        for (int k = lane; k < count; k += kWave) bmax = fmaxf(bmax, lp[sel_at(k)]);
+        bmax = wave_max_f(bmax);
+        const float ll_y2x = noreplacement_ll_sum(count, bmax, lane, [&](int k) { return lp[sel_at(count - 1 - k)]; });
+        const float log_acc = pisco_clamp0(((ll_y + ll_y2x) - ll_x) - ll_x2y);
+        const float ua = a.u_accept ? a.u_accept[b] : isco_unit(isco_draw(a.seed, genv, 0xFFFFFFFFu, 0, 2));
+        const bool accept = logf(ua + 1e-24f) < log_acc;
+        if (lane == 0) {
+            sc->want = accept ? 1 : 0;
+            if (a.energy_out) a.energy_out[b] = ll_y * T;
+            if (a.acc_out) a.acc_out[b] = expf(log_acc);
+            if (a.terms_out) {
+                float* t = a.terms_out + b * 5;
+                t[0] = ll_x; t[1] = ll_x2y; t[2] = ll_y; t[3] = ll_y2x; t[4] = log_acc;
+            }
+        }
+    }
+    __syncthreads();
+    const bool accept = sc->want != 0;
+    uint16_t* yo = a.y_out + b * N;
+    for (int64_t i = tid; i < N; i += NT) yo[i] = (accept ? yb[i] : xb[i]) ? 0x3C00 : 0;
+}
+
 // ----------------------------------------------------------------------------------------------- TSP
 struct IscoTspArgs {
     const float* dist; int64_t N; int32_t K; int32_t random_stride; float near_threshold;
@@ -908,6 +1287,66 @@ int rls_isco_mis_step(const rls_graph* g, const float* x, float* y_out, int64_t 
     RLS_REQUIRE(std::isfinite(lam), RLS_EINVAL, "lam must be finite");
     return isco_step_launch<IscoMis>(g, x, y_out, B, path_length, temperature, lam, u_gumbel, u_accept, seed, env_offset, energy_out,
                                      acc_out, terms_out, mask_out, scratch, scratch_bytes, stream);
+}
+
+// The dense step: the product, then isco_step_launch's choices (list capacity, wave or workgroup per sample, the same knobs) with the
+// rows in LDS only -- the rows-in-scratch form is not built for it (A alone would be 0.5 GB at its sizes).  Every check comes
+// before the first launch, and the checks that read no pointer (sizes, temperature, the LDS limit) before the pointer checks.
+int rls_pisco_step(const uint16_t* adj, int64_t Np, const uint16_t* x, uint16_t* y_out, int64_t B, const int64_t* path_length,
+                   float temperature, int32_t half_rounding, const float* u_gumbel, const float* u_accept, uint64_t seed,
+                   int64_t env_offset, float* energy_out, float* acc_out, float* terms_out, uint8_t* mask_out, void* scratch,
+                   int64_t scratch_bytes, void* stream) {
+    RLS_REQUIRE(Np > 0 && Np % 8 == 0 && Np < (1ll << 31), RLS_EINVAL, "Np=%lld must be a positive multiple of 8", (long long)Np);
+    RLS_REQUIRE(B >= 0, RLS_EINVAL, "B < 0");
+    if (B == 0) return RLS_OK;
+    RLS_REQUIRE(temperature > 0.0f, RLS_EINVAL, "temperature must be > 0");
+    const int64_t N = Np;
+    const size_t fixed = sizeof(IscoWgScratch) + 16;
+    const size_t rows = 2 * (size_t)N + (size_t)N * 8;
+    RLS_REQUIRE(rows + 64 * 8 + fixed <= (size_t)kLdsBytes, RLS_EUNSUPPORTED,
+                "Np=%lld: a sample's rows and the smallest list need %zu B of LDS (max %d); the dense step has no rows-in-scratch form",
+                (long long)N, rows + 64 * 8 + fixed, kLdsBytes);
+    RLS_REQUIRE(adj && x && y_out && path_length, RLS_EINVAL, "NULL pointer");
+    RLS_REQUIRE((u_gumbel == nullptr) == (u_accept == nullptr), RLS_EINVAL, "u_gumbel and u_accept must both be given or both be NULL");
+    RLS_REQUIRE((const void*)x != (const void*)y_out, RLS_EINVAL, "y_out must not alias x (a rejected proposal restores x)");
+    const int64_t need = rls_pisco_scratch_bytes(Np, B);
+    RLS_REQUIRE(scratch && scratch_bytes >= need, RLS_EINVAL, "Np=%lld B=%lld need %lld B of scratch (rls_pisco_scratch_bytes), got %lld",
+                (long long)Np, (long long)B, (long long)need, (long long)(scratch ? scratch_bytes : 0));
+    RLS_REQUIRE((((uintptr_t)scratch) & 15) == 0, RLS_EINVAL, "scratch must be 16-byte aligned");
+    float* r = static_cast<float*>(scratch);
+    int32_t* ord = reinterpret_cast<int32_t*>(r + B * Np);
+    if (int rc = rls_pisco_product(adj, Np, x, B, r, stream)) return rc;
+    const int force_cap = (int)knob(KN_ISCO_SEL_CAP, 0);
+    int P = 1;
+    while (P < N) P <<= 1;
+    if (P < 64) P = 64;
+    while (P > 64 && rows + (size_t)P * 8 + fixed > (size_t)kLdsBytes) P >>= 1;
+    if (force_cap >= 2 && force_cap < P && (force_cap & (force_cap - 1)) == 0) P = force_cap;
+    const size_t per_wave = rows + (size_t)P * 8;
+    const int force_wg = (int)knob(KN_ISCO_FORCE_WG, -1);
+    const bool use_wg = force_wg >= 0 ? (force_wg != 0 && N >= 4 * kWave) : (B <= (int64_t)2 * num_cus() || N >= 1536) && N >= 4 * kWave;
+    PiscoArgs a{adj, N, x, y_out, B, path_length, temperature, half_rounding, u_gumbel, u_accept, seed, env_offset,
+                energy_out, acc_out, terms_out, mask_out, P, r, ord};
+    if (use_wg) {
+        const size_t lds_wg = per_wave + fixed;
+        ensure_dyn_lds((const void*)k_pisco_step_wg, lds_wg);
+        hipLaunchKernelGGL(k_pisco_step_wg, dim3((unsigned)B), dim3(kIscoWgWaves * kWave), lds_wg, as_stream(stream), a);
+        return check_launch("k_pisco_step_wg");
+    }
+    const int max_waves = (int)knob(KN_ISCO_WAVES, 8);
+    auto waves_for = [&](int cap) {
+        int wv = (int)((size_t)kLdsBytes / (rows + (size_t)cap * 8));
+        return wv > max_waves ? max_waves : wv;
+    };
+    int Pw = P;
+    if (force_cap == 0)
+        while (Pw > 512 && waves_for(Pw >> 1) > waves_for(Pw)) Pw >>= 1;
+    const int waves = waves_for(Pw) < 1 ? 1 : waves_for(Pw);
+    a.P = Pw;
+    const size_t lds = (rows + (size_t)Pw * 8) * waves;
+    ensure_dyn_lds((const void*)k_pisco_step, lds);
+    hipLaunchKernelGGL(k_pisco_step, dim3((unsigned)ceil_div(B, waves)), dim3(waves * kWave), lds, as_stream(stream), a);
+    return check_launch("k_pisco_step");
 }
 
 int rls_isco_tsp_step(const float* dist, int64_t N, const int32_t* nearest, int32_t K, float near_threshold, const int32_t* random,

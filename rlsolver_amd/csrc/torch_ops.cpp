@@ -1019,6 +1019,52 @@ void isco_mis_step(int64_t g, const Tensor& x, Tensor y_out, const Tensor& path_
                          (float*)p(acc_out), (float*)p(terms_out), (uint8_t*)p(mask_out), p(scratch),
                          scratch.has_value() ? (int64_t)scratch->nbytes() : 0, cur_stream(x)), "rls_isco_mis_step");
 }
+// PISCO_maxcut: the dense product and the step over it (f16 matrix and samples)
+static int64_t pisco_shapes(const Tensor& adj, const Tensor& x) {
+    dev(adj, "adj", at::kHalf);
+    dev(x, "x", at::kHalf);
+    same_device(adj, x, "x");
+    TORCH_CHECK(adj.dim() == 2 && adj.size(0) == adj.size(1) && adj.size(0) > 0 && adj.size(0) % 8 == 0,
+                "adj must be [Np, Np] with Np a positive multiple of 8, got ", adj.sizes());
+    TORCH_CHECK(x.dim() == 2 && x.size(1) == adj.size(0), "x must be [B, ", adj.size(0), "], got ", x.sizes());
+    return x.size(0);
+}
+void pisco_product(const Tensor& adj, const Tensor& x, Tensor r_out) {
+    const int64_t B = pisco_shapes(adj, x), Np = adj.size(0);
+    dev(r_out, "r_out", F32);
+    same_device(x, r_out, "r_out");
+    shape2(r_out, "r_out", B, Np);
+    RLS_GUARD(x);
+    ok(rls_pisco_product((const uint16_t*)p(adj), Np, (const uint16_t*)p(x), B, (float*)p(r_out), cur_stream(x)), "rls_pisco_product");
+}
+void pisco_step(const Tensor& adj, const Tensor& x, Tensor y_out, const Tensor& path_length, double temperature, bool half_rounding,
+                const OptTensor& u_gumbel, const OptTensor& u_accept, int64_t seed, int64_t env_offset, const OptTensor& energy_out,
+                const OptTensor& acc_out, const OptTensor& terms_out, const OptTensor& mask_out, Tensor scratch) {
+    const int64_t B = pisco_shapes(adj, x), Np = adj.size(0);
+    dev(y_out, "y_out", at::kHalf);
+    dev(path_length, "path_length", I64);
+    optdev(u_gumbel, "u_gumbel", F32);
+    optdev(u_accept, "u_accept", F32);
+    optdev(energy_out, "energy_out", F32);
+    optdev(acc_out, "acc_out", F32);
+    optdev(terms_out, "terms_out", F32);
+    TORCH_CHECK(y_out.sizes() == x.sizes(), "y_out must have the shape of x");
+    same_device(x, y_out, "y_out");
+    count(path_length, "path_length", B);
+    TORCH_CHECK(u_gumbel.has_value() == u_accept.has_value(), "u_gumbel and u_accept must be given together");
+    if (u_gumbel.has_value()) { shape2(*u_gumbel, "u_gumbel", B, Np); count(*u_accept, "u_accept", B); }
+    if (energy_out.has_value()) count(*energy_out, "energy_out", B);
+    if (acc_out.has_value()) count(*acc_out, "acc_out", B);
+    if (terms_out.has_value()) shape2(*terms_out, "terms_out", B, 5);
+    if (mask_out.has_value()) { spin_bytes(*mask_out, "mask_out", false); shape2(*mask_out, "mask_out", B, Np); }
+    dev(scratch, "scratch");
+    same_device(x, scratch, "scratch");
+    RLS_GUARD(x);
+    ok(rls_pisco_step((const uint16_t*)p(adj), Np, (const uint16_t*)p(x), (uint16_t*)p(y_out), B, (const int64_t*)p(path_length),
+                      (float)temperature, half_rounding ? 1 : 0, (const float*)p(u_gumbel), (const float*)p(u_accept), (uint64_t)seed,
+                      env_offset, (float*)p(energy_out), (float*)p(acc_out), (float*)p(terms_out), (uint8_t*)p(mask_out), p(scratch),
+                      (int64_t)scratch.nbytes(), cur_stream(x)), "rls_pisco_step");
+}
 void isco_tsp_step(const Tensor& dist, const Tensor& nearest, double near_threshold, const Tensor& random, const Tensor& perm_in, Tensor perm_out,
                    int64_t path_length, double temperature, const OptTensor& u_partner, const OptTensor& r_near, const OptTensor& r_rand,
                    const OptTensor& u_gumbel, const OptTensor& u_accept, int64_t seed, int64_t env_offset, const OptTensor& log_acc_out,
@@ -1140,6 +1186,10 @@ TORCH_LIBRARY(rlsolver_hip, m) {
           "int chain_offset=0, int chain_period=0, int chain_skip=0) -> ()");
     m.def("isco_mis_step(int graph, Tensor x, Tensor(a!) y_out, Tensor path_length, float temperature, float lam, Tensor? u_gumbel, Tensor? u_accept, "
           "int seed, int env_offset, Tensor(b!)? energy_out, Tensor(c!)? acc_out, Tensor(d!)? terms_out, Tensor(e!)? mask_out, Tensor(f!)? scratch=None) -> ()");
+    m.def("pisco_product(Tensor adj, Tensor x, Tensor(a!) r_out) -> ()");
+    m.def("pisco_step(Tensor adj, Tensor x, Tensor(a!) y_out, Tensor path_length, float temperature, bool half_rounding, Tensor? u_gumbel, "
+          "Tensor? u_accept, int seed, int env_offset, Tensor(b!)? energy_out, Tensor(c!)? acc_out, Tensor(d!)? terms_out, Tensor(e!)? mask_out, "
+          "Tensor(f!) scratch) -> ()");
     m.def("isco_tsp_step(Tensor dist, Tensor nearest, float near_threshold, Tensor random, Tensor perm_in, Tensor(a!) perm_out, int path_length, "
           "float temperature, Tensor? u_partner, Tensor? r_near, Tensor? r_rand, Tensor? u_gumbel, Tensor? u_accept, int seed, int env_offset, "
           "Tensor(b!)? log_acc_out, Tensor(c!)? acc_out, Tensor(d!)? cur_out) -> ()");
@@ -1201,4 +1251,6 @@ TORCH_LIBRARY_IMPL(rlsolver_hip, CUDA, m) {   // "CUDA" is the HIP dispatch key 
     m.impl("mimo_local_search", &mimo_local_search);
     m.impl("maxcut_edge_local_search", &maxcut_edge_local_search);
     m.impl("isco_tsp_step", &isco_tsp_step);
+    m.impl("pisco_product", &pisco_product);
+    m.impl("pisco_step", &pisco_step);
 }

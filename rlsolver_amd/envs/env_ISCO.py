@@ -119,4 +119,7 @@ def __getattr__(name):
     if name == "ISCO_MIS":          # env_ISCO.py:93-174
         from .env_ISCO_MIS import ISCO_MIS
         return ISCO_MIS
+    if name == "PISCO_maxcut":      # env_ISCO.py:365-448
+        from .env_PISCO_maxcut import PISCO_maxcut
+        return PISCO_maxcut
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

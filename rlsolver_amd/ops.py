@@ -442,3 +442,50 @@ def rand_actions(B: int, N: int, seed: int, step: int, device, env_offset: int =
     _check(out, "out", (torch.int64,), None, (B,))
     _t.rand_actions(out, N, _s64(seed), _s64(step), env_offset)
     return out
+
+
+# ---- PISCO_maxcut: the dense f16 product and the sampler step over it (rls_pisco_product / rls_pisco_step)
+def pisco_scratch_bytes(Np: int, B: int) -> int:
+    return int(_abi.lib().rls_pisco_scratch_bytes(int(Np), int(B)))
+
+
+def _pisco_operands(adj: TEN, x: TEN):
+    adj = _check(adj, "adj", (torch.float16,))
+    if adj.dim() != 2 or adj.shape[0] != adj.shape[1] or adj.shape[0] == 0 or adj.shape[0] % 8:
+        raise ValueError(f"adj must be [Np, Np] with Np a positive multiple of 8, got {tuple(adj.shape)}")
+    x = _check(x, "x", (torch.float16,), adj.device)
+    if x.dim() != 2 or x.shape[1] != adj.shape[0]:
+        raise ValueError(f"x must be [B, {adj.shape[0]}], got {tuple(x.shape)}")
+    return adj, x
+
+
+def pisco_product(adj: TEN, x: TEN, out: Optional[TEN] = None) -> TEN:
+    """r f32 [B, Np] = (2x - 1) . adj on the f16 matrix cores (env_ISCO.py:439); adj f16 [Np, Np], x f16 [B, Np] holding 0|1."""
+    adj, x = _pisco_operands(adj, x)
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    _t.pisco_product(adj, x, _check(out, "out", (torch.float32,), x.device, x.shape))
+    return out
+
+
+def pisco_step(adj: TEN, x: TEN, path_length: TEN, temperature: float, half_rounding: bool = True, u_gumbel: Optional[TEN] = None,
+               u_accept: Optional[TEN] = None, seed: int = 0, env_offset: int = 0, want_terms: bool = False,
+               scratch: Optional[TEN] = None):
+    """PISCO_maxcut.step (env_ISCO.py:384-392) -> (y f16 [B, Np], ll_y * T f32 [B], acceptance probability f32 [B]) and, with
+    ``want_terms``, (terms f32 [B, 5], mask bool [B, Np]).  ``scratch``: uint8, pisco_scratch_bytes(Np, B) (allocated if None)."""
+    adj, x = _pisco_operands(adj, x)
+    B, Np = x.shape
+    dev = x.device
+    pl = _check(path_length, "path_length", (torch.int64,), dev, (B,))
+    if scratch is None:
+        scratch = torch.empty(max(pisco_scratch_bytes(Np, B), 16), dtype=torch.uint8, device=dev)
+    y = torch.empty_like(x)
+    energy = torch.empty(B, dtype=torch.float32, device=dev)
+    acc = torch.empty(B, dtype=torch.float32, device=dev)
+    terms = torch.empty((B, 5), dtype=torch.float32, device=dev) if want_terms else None
+    mask = torch.empty((B, Np), dtype=torch.bool, device=dev) if want_terms else None
+    _t.pisco_step(adj, x, y, pl, float(temperature), bool(half_rounding), u_gumbel, u_accept, _s64(seed), int(env_offset),
+                  energy, acc, terms, mask, scratch)
+    if want_terms:
+        return y, energy, acc, terms, mask
+    return y, energy, acc

@@ -1556,6 +1556,106 @@ def gen_isco_mis():
     save("isco_mis", **out)
 
 
+def gen_pisco():
+    """PISCO_maxcut (envs/env_ISCO.py:365-448), the reference's own class on the CPU (its half matmul and autograd run there):
+    get_local_dist at two temperatures and three full steps with every torch draw recorded, the five terms, the mask and the
+    proposal captured by wrapping the instance's proposal / ll_y2x / select_sample.  The matrix is built in numpy and handed over
+    as adj_matrix: (a) BA_100_ID0, the default DATAPATH, unit weights, Np = 104; (b) 20 nodes, weights in +-3, Np = 24; (c) 61
+    nodes, 90 % dense, weights 1..60, started from the all-ones sample so that entries of r exceed 2048 and are odd -- the f16
+    rounding of r itself is exercised."""
+    import rlsolver.envs.env_ISCO as env_isco
+    from rlsolver.methods.util_read_data import read_mygraph
+    B = 12
+    env_isco.BATCH_SIZE = B
+    env_isco.DEVICE = th.device("cpu")
+
+    def dense(n, edges):
+        Np = (n + 7) // 8 * 8
+        A = np.zeros((Np, Np), np.float64)
+        for u, v, w in edges:
+            A[u, v] = A[v, u] = w
+        return A.astype(np.float16)
+
+    cases = []
+    g = graph_arrays(read_mygraph(os.path.join(DATA, GRAPHS["BA_100_ID0"])))
+    cases.append(("BA_100_ID0", int(g[:, :2].max()) + 1, [(int(u), int(v), 1) for u, v, _ in g], None))
+    r = np.random.RandomState(20)
+    e20 = [(u, v, int(r.choice([-3, -2, -1, 1, 2, 3]))) for u in range(20) for v in range(u + 1, 20) if r.rand() < 0.3]
+    cases.append(("w3_20", 20, e20, None))
+    r = np.random.RandomState(62)       # the first seed from 61 on whose graph has an odd row sum past 2048 (asserted below)
+    e61 = [(u, v, int(r.randint(1, 61))) for u in range(61) for v in range(u + 1, 61) if r.rand() < 0.9]
+    cases.append(("dense_61", 61, e61, "ones"))
+    out = {}
+    for cname, n, edges, start in cases:
+        A = dense(n, edges)
+        Np = A.shape[0]
+        eu = th.tensor([e[0] for e in edges], dtype=th.int64)
+        ev = th.tensor([e[1] for e in edges], dtype=th.int64)
+        params = {"num_nodes": n, "num_edges": len(edges), "edge_from": eu, "edge_to": ev, "adj_matrix": th.from_numpy(A.copy())}
+        smp = env_isco.PISCO_maxcut(params)
+        out[f"{cname}/adj"] = A
+        out[f"{cname}/num_nodes"] = np.int64(n)
+        out[f"{cname}/edges"] = np.array(edges, dtype=np.int64)
+        th.manual_seed(5)
+        x = smp.random_gen_init_sample()
+        assert x.dtype == th.float16 and tuple(x.shape) == (B, n)
+        if start == "ones":
+            x = th.ones_like(x)
+        x = th.nn.functional.pad(x, (0, Np - n), mode="constant", value=0)          # main_PISCO_maxcut.py:23-24
+        if start == "ones":
+            r0 = (x.double() * 2 - 1) @ th.from_numpy(A.astype(np.float64))
+            big_odd = (r0.abs() > 2048) & (r0.long() % 2 == 1)
+            assert bool(big_odd.any()), "no entry of r is odd and past 2048: the f16 rounding of r would not be exercised"
+        out[f"{cname}/x"] = u8(x)
+        out[f"{cname}/x_dtype"] = np.array(str(x.dtype))
+        for T in (1.0, 0.37):
+            energy, logp = smp.get_local_dist(x, th.tensor(T))
+            out[f"{cname}/T{T}/energy"] = energy.numpy().copy()
+            out[f"{cname}/T{T}/log_prob"] = logp.numpy().copy()
+        cap = {}
+        o_prop, o_y2x, o_sel = smp.proposal, smp.ll_y2x, smp.select_sample
+
+        def w_prop(x, pl, T):
+            r = o_prop(x, pl, T)
+            cap["ll_x"], cap["y_prop"] = r[0].clone(), r[1].clone()
+            cap["ll_x2y"], cap["mask"] = r[2]["ll_x2y"].clone(), r[2]["selected_idx"]["selected_mask"].clone()
+            return r
+
+        def w_y2x(tr, y, T):
+            r = o_y2x(tr, y, T)
+            cap["ll_y"], cap["ll_y2x"] = r[0].clone(), r[1].clone()
+            return r
+
+        def w_sel(la, x, y):
+            cap["log_acc"] = la.clone()
+            return o_sel(la, x, y)
+
+        smp.proposal, smp.ll_y2x, smp.select_sample = w_prop, w_y2x, w_sel
+        gen = th.Generator().manual_seed(15)
+        for k, T in enumerate((1.0, 0.5, 0.2)):
+            pl = th.randint(1, min(n, 14), (B,), generator=gen)
+            pl[0], pl[1] = 1, Np                     # the two ends of the clamp; Np: every column, the padded ones too
+            th.manual_seed(100 + k)
+            with Recorder("rand") as rec:
+                y, energy, acc = smp.step(x, pl, th.tensor(T))
+            assert len(rec.log["rand"]) == 2 and y.dtype == th.float16 and tuple(y.shape) == (B, Np)
+            tag = f"{cname}/step{k}"
+            out[f"{tag}/x"] = u8(x)
+            out[f"{tag}/path_length"] = pl.numpy().copy()
+            out[f"{tag}/temperature"] = np.float32(T)
+            out[f"{tag}/rand_gumbel"] = rec.log["rand"][0].numpy().copy()
+            out[f"{tag}/rand_accept"] = rec.log["rand"][1].numpy().copy()
+            for kk in ("ll_x", "ll_x2y", "ll_y", "ll_y2x", "log_acc"):
+                out[f"{tag}/{kk}"] = cap[kk].numpy().copy()
+            out[f"{tag}/mask"] = u8(cap["mask"])
+            out[f"{tag}/y_prop"] = u8(cap["y_prop"])
+            out[f"{tag}/y"] = u8(y)
+            out[f"{tag}/energy"] = energy.numpy().copy()
+            out[f"{tag}/acc"] = acc.numpy().copy()
+            x = y
+    save("pisco", **out)
+
+
 API_FILES = (
     "rlsolver/envs/env_L2A.py", "rlsolver/envs/env_MCPG.py", "rlsolver/envs/env_PPO.py", "rlsolver/envs/env_ISCO.py",
     "rlsolver/methods/LocalSearch.py", "rlsolver/methods/MCPG.py", "rlsolver/methods/util_evaluator.py",
@@ -2035,7 +2135,7 @@ def gen_mimo():
 ALL = {"graph_forms": gen_graph_forms, "mimo": gen_mimo, "cheeger": gen_cheeger, "maxcut_edge": gen_maxcut_edge, "maxsat": gen_maxsat, "mcpg_weighted": gen_mcpg_weighted, "isco_steps": gen_isco_steps, "isco_mis": gen_isco_mis, "spinsystem_cpu": gen_spinsystem_cpu, "spinsystem": gen_spinsystem, "spinsystem_perenv": gen_spinsystem_perenv, "qubo": gen_qubo, "qubo_asym": gen_qubo_asym, "isco_maxcut": gen_isco_maxcut, "maxcut": gen_maxcut, "sweep": gen_sweep, "lsclass": gen_local_search_class, "ppo": gen_ppo,
        "select": gen_select, "mcpg": gen_mcpg, "tsp": gen_tsp, "tsp_2opt": gen_tsp_2opt, "encoder": gen_encoder,
        "wgain": gen_weighted_gain, "mcpg_glue": gen_mcpg_glue, "evaluator": gen_evaluator, "spinsystem_options": gen_spinsystem_options,
-       "api_surface": gen_api_surface, "mcpg_data": gen_mcpg_data,
+       "api_surface": gen_api_surface, "mcpg_data": gen_mcpg_data, "pisco": gen_pisco,
        "spinsystem_inference": gen_spinsystem_inference, "spinsystem_s2v": gen_spinsystem_s2v}
 
 if __name__ == "__main__":
