@@ -3,6 +3,8 @@
 //                          (get_local_dist :51-63, proposal :37-49, ll_y2x :65-77)
 //   rls_isco_mis_step    : ISCO_MIS.step      rlsolver/envs/env_ISCO.py:111-174: the MaxCut step's kernels with the energy
 //                          model (:162-170) as a template parameter
+//   rls_pisco_step       : PISCO_maxcut.step  rlsolver/envs/env_ISCO.py:384-434: the same two bodies on f16 samples, the local
+//                          distribution read from a row of the dense product
 //   rls_isco_tsp_step    : ISCO_TSP.step      rlsolver/envs/env_ISCO.py:188-236 (opt_2 :238-335, switch :337-344)
 // with the sampler helpers of rlsolver/methods/util.py:498-570 (gumbel, log1mexp,
 // noreplacement_sampling_renormalize, multinomial, bernoulli_logp, mh_step) folded in.  The reference runs each
@@ -19,6 +21,7 @@
 #include "rls_tile.h"
 #include "rls_draw.h"
 #include "rls_tsp_plan.h"
+#include "rls_isco_plan.h"
 #include <cmath>
 #include <cstdlib>
 
@@ -77,6 +80,195 @@ __device__ __forceinline__ float noreplacement_ll_sum(int count, float base, int
     return wave_sum_f32x(total);
 }
 
+// ----------------------------------------------------------------------------------------------- the stages of a step
+// A step on a graph or on a dense matrix is one pipeline: binarise the row | local distribution into lp[] | Gumbel perturbation
+// into pert[] | the key of the L-th largest perturbed value | the selected set compacted into the LDS list | the list sorted (or,
+// larger than the list, ordered by extraction) | ll_x2y, the flip, the backward distribution | ll_y2x | Metropolis-Hastings.
+// Each stage is written once (the select and the compaction once per team shape: a wave, or a workgroup with its IscoWgScratch).
+
+__device__ __forceinline__ float isco_block_max(float v, IscoWgScratch* sc, int lane, int w) {
+    v = wave_max_f(v);
+    __syncthreads();
+    if (lane == 0) sc->f[w] = v;
+    __syncthreads();
+    float m = sc->f[0];
+#pragma unroll
+    for (int k = 1; k < kIscoWgWaves; ++k) m = fmaxf(m, sc->f[k]);
+    return m;
+}
+__device__ __forceinline__ float isco_block_sum(float v, IscoWgScratch* sc, int lane, int w) {
+    v = wave_sum_f32x(v);
+    __syncthreads();
+    if (lane == 0) sc->f[w] = v;
+    __syncthreads();
+    float m = 0.0f;
+#pragma unroll
+    for (int k = 0; k < kIscoWgWaves; ++k) m += sc->f[k];
+    return m;
+}
+__device__ __forceinline__ int isco_block_sum_i(int v, IscoWgScratch* sc, int lane, int w) {
+    v = wave_sum_i32(v);
+    __syncthreads();
+    if (lane == 0) sc->i[w] = v;
+    __syncthreads();
+    int m = 0;
+#pragma unroll
+    for (int k = 0; k < kIscoWgWaves; ++k) m += sc->i[k];
+    return m;
+}
+
+// Threshold = the key of the `want`-th largest perturbed value (util.py:518-523): radix select on the monotone key.
+// One wave: 32 one-bit passes.
+__device__ __forceinline__ uint32_t isco_threshold_wave(const float* pert, int64_t N, int want, int lane) {
+    uint32_t prefix = 0;
+    if (N <= 32 * kWave) {
+        // the lane's <= 32 keys in registers for the 32 bit passes (re-reading them from LDS put an LDS round trip on
+        // every element of every pass); key 0 (out of range) has no bit set and is never counted
+        uint32_t kk[32];
+#pragma unroll
+        for (int j = 0; j < 32; ++j) {
+            const int64_t i = lane + (int64_t)j * kWave;
+            kk[j] = i < N ? fkey(pert[i]) : 0u;
+        }
+        for (int bit = 31; bit >= 0; --bit) {
+            const uint32_t hi_mask = bit == 31 ? 0u : (0xFFFFFFFFu << (bit + 1));
+            int cnt = 0;
+#pragma unroll
+            for (int j = 0; j < 32; ++j) cnt += ((kk[j] & hi_mask) == prefix) && ((kk[j] >> bit) & 1u);
+            cnt = wave_sum_i32(cnt);
+            if (cnt >= want) prefix |= 1u << bit;              // the L-th largest has this bit set
+            else want -= cnt;
+        }
+    } else {
+        for (int bit = 31; bit >= 0; --bit) {
+            const uint32_t hi_mask = bit == 31 ? 0u : (0xFFFFFFFFu << (bit + 1));
+            int cnt = 0;
+            for (int64_t i = lane; i < N; i += kWave) {
+                const uint32_t k = fkey(pert[i]);
+                cnt += ((k & hi_mask) == prefix) && ((k >> bit) & 1u);
+            }
+            cnt = wave_sum_i32(cnt);
+            if (cnt >= want) prefix |= 1u << bit;              // the L-th largest has this bit set
+            else want -= cnt;
+        }
+    }
+    return prefix;
+}
+
+// ... a workgroup: four 8-bit histogram passes (LDS atomics); wave 0 reads each histogram
+__device__ __forceinline__ uint32_t isco_threshold_wg(const float* pert, int64_t N, int want, IscoWgScratch* sc, int lane, int w, int tid) {
+    constexpr int NT = kIscoWgWaves * kWave;
+    uint32_t prefix = 0;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        const uint32_t hi_mask = shift == 24 ? 0u : (0xFFFFFFFFu << (shift + 8));
+        for (int k = tid; k < 256; k += NT) sc->hist[k] = 0;
+        __syncthreads();
+        for (int64_t i = tid; i < N; i += NT) {
+            const uint32_t k = fkey(pert[i]);
+            if ((k & hi_mask) == prefix) atomicAdd(&sc->hist[(k >> shift) & 255u], 1);
+        }
+        __syncthreads();
+        if (w == 0) {   // the largest byte value v whose suffix count (entries with byte >= v) reaches `want`
+            int c[4], tot = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { c[q] = sc->hist[lane * 4 + q]; tot += c[q]; }
+            int suf = tot;                                        // inclusive suffix sum over lanes: lanes >= this one
+#pragma unroll
+            for (int d = 1; d < kWave; d <<= 1) {
+                const int o = __shfl_down(suf, d, 64);
+                if (lane + d < kWave) suf += o;
+            }
+            const int above = suf - tot;                          // entries in bins of higher lanes
+            // inside this lane's four bins, from the top
+            int byte_found = -1, want_left = 0, run = above;
+#pragma unroll
+            for (int q = 3; q >= 0; --q) {
+                if (byte_found < 0 && run < want && run + c[q] >= want) { byte_found = lane * 4 + q; want_left = want - run; }
+                run += c[q];
+            }
+            if (byte_found >= 0) { sc->prefix = prefix | ((uint32_t)byte_found << shift); sc->want = want_left; }
+        }
+        __syncthreads();
+        prefix = sc->prefix;
+        want = sc->want;
+    }
+    return prefix;
+}
+
+// The selected set (perturbed >= threshold) compacted into the list, as much of it as the list holds; returns its size.
+// One wave: ballot / popcount, in node order.
+__device__ __forceinline__ int isco_compact_wave(const float* pert, int64_t N, uint32_t prefix, float* skey, int32_t* sidx, int P,
+                                                 int lane) {
+    int count = 0;
+    for (int64_t i0 = 0; i0 < N; i0 += kWave) {
+        const int64_t i = i0 + lane;
+        const bool sel = i < N && fkey(pert[i]) >= prefix;
+        const uint64_t m = ballot64(sel);
+        if (sel) {
+            const int at = count + __popcll(m & ((1ull << lane) - 1ull));
+            if (at < P) {
+                skey[at] = pert[i];
+                sidx[at] = (int)i;
+            }
+        }
+        count += __popcll(m);
+    }
+    return count;
+}
+
+// ... a workgroup: a counter in LDS, any order (sorted next, equal keys by node id)
+__device__ __forceinline__ int isco_compact_wg(const float* pert, int64_t N, uint32_t prefix, float* skey, int32_t* sidx, int P,
+                                               IscoWgScratch* sc, int tid) {
+    constexpr int NT = kIscoWgWaves * kWave;
+    if (tid == 0) sc->count = 0;
+    __syncthreads();
+    for (int64_t i = tid; i < N; i += NT) {
+        if (fkey(pert[i]) >= prefix) {
+            const int at = atomicAdd(&sc->count, 1);
+            if (at < P) {
+                skey[at] = pert[i];
+                sidx[at] = (int)i;
+            }
+        }
+    }
+    __syncthreads();
+    return sc->count;
+}
+
+// The list sorted by perturbed value, descending, by ONE wave: padded to a power of two, bitonic.
+// TIE: equal keys order by node id (lowest first, as the extraction), so that the result does not depend on the compaction order.
+template <bool TIE>
+__device__ __forceinline__ void isco_sort_list(float* skey, int32_t* sidx, int count, int lane) {
+    int P2 = 1;
+    while (P2 < count) P2 <<= 1;
+    for (int k = count + lane; k < P2; k += kWave) { skey[k] = -INFINITY; sidx[k] = -1; }
+    lds_fence();
+    for (int size = 2; size <= P2; size <<= 1) {
+        for (int stride = size >> 1; stride >= 1; stride >>= 1) {
+            for (int t = lane; t < (P2 >> 1); t += kWave) {
+                const int lo = ((t / stride) * (stride << 1)) + (t % stride);
+                const int hi = lo + stride;
+                const bool desc = ((lo & size) == 0);
+                const float k0 = skey[lo], k1 = skey[hi];
+                if constexpr (TIE) {
+                    const int i0 = sidx[lo], i1 = sidx[hi];
+                    const bool lt = (k0 < k1) || (k0 == k1 && i0 > i1);
+                    if (lt == desc) {
+                        skey[lo] = k1; skey[hi] = k0;
+                        sidx[lo] = i1; sidx[hi] = i0;
+                    }
+                } else {
+                    if ((k0 < k1) == desc) {
+                        skey[lo] = k1; skey[hi] = k0;
+                        const int t0 = sidx[lo]; sidx[lo] = sidx[hi]; sidx[hi] = t0;
+                    }
+                }
+            }
+            lds_fence();
+        }
+    }
+}
+
 // Order of a selection that does not fit the LDS list (count > capacity: path lengths in the thousands on a graph whose
 // rows nearly fill LDS -- the reference draws Poisson(~10) path lengths, main_ISCO_maxcut.py:22-30): repeated extraction of
 // the maximum, O(count N / 64) per sample, ONE wave.  The node ids leave in order into `ord` -- global scratch: for the graph
@@ -106,7 +298,35 @@ __device__ __noinline__ void isco_order_by_extraction(const float* pert, uint8_t
     __threadfence();      // the list is read back by every lane (and, in the workgroup kernel, by every wave after a barrier)
 }
 
-// ----------------------------------------------------------------------------------------------- MaxCut
+// ll_y2x: the log-probability of undoing the selection in reverse order under the backward distribution lp (env_ISCO.py:65-77);
+// its ll_base is the maximum over the selected entries.  ONE wave.
+template <typename S>
+__device__ __forceinline__ float isco_reverse_ll(const float* lp, int count, S sel_at, int lane) {
+    float bmax = -INFINITY;
+    for (int k = lane; k < count; k += kWave) bmax = fmaxf(bmax, lp[sel_at(k)]);
+    bmax = wave_max_f(bmax);
+    return noreplacement_ll_sum(count, bmax, lane, [&](int k) { return lp[sel_at(count - 1 - k)]; });
+}
+
+// Metropolis-Hastings accept (env_ISCO.py:31-33, util.py:556-570) from the four terms and the clamped log-acceptance; lane 0
+// publishes the energy, the acceptance probability and the five terms.  ONE wave; every lane returns the decision.
+template <class A>
+__device__ __forceinline__ bool isco_mh_accept(const A& a, int64_t b, float ll_x, float ll_x2y, float ll_y, float ll_y2x, float log_acc,
+                                               int lane) {
+    const float ua = a.u_accept ? a.u_accept[b] : isco_unit(isco_draw(a.seed, (uint64_t)(b + a.env_offset), 0xFFFFFFFFu, 0, 2));
+    const bool accept = logf(ua + 1e-24f) < log_acc;
+    if (lane == 0) {
+        if (a.energy_out) a.energy_out[b] = ll_y * a.temperature;   // the reference returns ll_y * temperature of the PROPOSAL
+        if (a.acc_out) a.acc_out[b] = expf(log_acc);
+        if (a.terms_out) {
+            float* t = a.terms_out + b * 5;
+            t[0] = ll_x; t[1] = ll_x2y; t[2] = ll_y; t[3] = ll_y2x; t[4] = log_acc;
+        }
+    }
+    return accept;
+}
+
+// ----------------------------------------------------------------------------------------------- MaxCut / MIS on a graph
 // LDS per wave: xb[N] yb[N] bytes (padded to 8) | lp[N] f32 | pert[N] f32 | sel_key[P] f32 | sel_idx[P] i32,
 // P = the list's capacity: the next power of two >= N while that fits LDS, else the largest power of two that does
 // (N = 10^4, G70: 4096 entries).  A selection larger than P takes isco_order_by_extraction.
@@ -231,190 +451,6 @@ __device__ __forceinline__ float isco_local_dist(const uint8_t* s, float* lp, in
     return M::ll(acc, temperature, lam, [](int v) { return wave_sum_i32(v); });
 }
 
-template <class M>
-__global__ __launch_bounds__(512) void k_isco_maxcut_step(IscoMcArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wib = threadIdx.x / kWave;
-    const int64_t b = (int64_t)blockIdx.x * (blockDim.x / kWave) + wib;
-    if (b >= a.B) return;
-    const int64_t N = a.N;
-    const int P = a.P;
-    const size_t nb8 = ((size_t)N + 7) & ~(size_t)7;
-    const size_t per_wave = 2 * nb8 + (size_t)N * 8 + (size_t)P * 8;
-    unsigned char* base = smem + (size_t)wib * per_wave;
-    uint8_t* xb = base;
-    uint8_t* yb = base + nb8;
-    float* lp = reinterpret_cast<float*>(base + 2 * nb8);
-    float* pert = lp + N;
-    float* skey = pert + N;
-    int32_t* sidx = reinterpret_cast<int32_t*>(skey + P);
-    const float* xr = a.x + b * N;
-    const float T = a.temperature;
-    const uint64_t genv = (uint64_t)(b + a.env_offset);
-
-    for (int64_t i = lane; i < N; i += kWave) xb[i] = xr[i] > 0.0f ? 1 : 0;
-    lds_fence();
-    // ---- forward: ll_x, proposal distribution, Gumbel perturbation (env_ISCO.py:51-63, util.py:498-516)
-    const float ll_x = isco_local_dist<M>(xb, lp, N, a.rowptr, a.col, a.ell_ptr, a.ell, T, a.lam, lane);
-    float lmax = -INFINITY;
-    for (int64_t i = lane; i < N; i += kWave) {
-        const float u = a.u_gumbel ? a.u_gumbel[b * N + i] : isco_unit(isco_draw(a.seed, genv, (uint32_t)i, 0, 1));
-        const float l = lp[i];
-        pert[i] = l - logf(-logf(u));
-        lmax = fmaxf(lmax, l);
-    }
-    lmax = wave_max_f(lmax);                                   // ll_base of the forward renormalisation: max over ALL entries
-    lds_fence();
-    // ---- threshold = L-th largest perturbed value (util.py:518-523): radix select on the monotone key
-    int64_t L = a.path_length[b];
-    L = L < 1 ? 1 : (L > N ? N : L);
-    uint32_t prefix = 0;
-    int want = (int)L;
-    if (N <= 32 * kWave) {
-        // the lane's <= 32 keys in registers for the 32 bit passes (re-reading them from LDS put an LDS round trip on
-        // every element of every pass); key 0 (out of range) has no bit set and is never counted
-        uint32_t kk[32];
-#pragma unroll
-        for (int j = 0; j < 32; ++j) {
-            const int64_t i = lane + (int64_t)j * kWave;
-            kk[j] = i < N ? fkey(pert[i]) : 0u;
-        }
-        for (int bit = 31; bit >= 0; --bit) {
-            const uint32_t hi_mask = bit == 31 ? 0u : (0xFFFFFFFFu << (bit + 1));
-            int cnt = 0;
-#pragma unroll
-            for (int j = 0; j < 32; ++j) cnt += ((kk[j] & hi_mask) == prefix) && ((kk[j] >> bit) & 1u);
-            cnt = wave_sum_i32(cnt);
-            if (cnt >= want) prefix |= 1u << bit;              // the L-th largest has this bit set
-            else want -= cnt;
-        }
-    } else {
-        for (int bit = 31; bit >= 0; --bit) {
-            const uint32_t hi_mask = bit == 31 ? 0u : (0xFFFFFFFFu << (bit + 1));
-            int cnt = 0;
-            for (int64_t i = lane; i < N; i += kWave) {
-                const uint32_t k = fkey(pert[i]);
-                cnt += ((k & hi_mask) == prefix) && ((k >> bit) & 1u);
-            }
-            cnt = wave_sum_i32(cnt);
-            if (cnt >= want) prefix |= 1u << bit;              // the L-th largest has this bit set
-            else want -= cnt;
-        }
-    }
-    // ---- selected set (perturbed >= threshold), compacted then sorted by perturbed value, descending
-    int count = 0;
-    for (int64_t i0 = 0; i0 < N; i0 += kWave) {
-        const int64_t i = i0 + lane;
-        const bool sel = i < N && fkey(pert[i]) >= prefix;
-        const uint64_t m = ballot64(sel);
-        if (sel) {
-            const int at = count + __popcll(m & ((1ull << lane) - 1ull));
-            if (at < P) {
-                skey[at] = pert[i];
-                sidx[at] = (int)i;
-            }
-        }
-        count += __popcll(m);
-    }
-    const bool big = count > P;                                  // (wave-uniform) the list does not hold the selection
-    int32_t* ord = reinterpret_cast<int32_t*>(a.y_out + b * N);  // its order then lives in this sample's output row until the end
-    if (big) {
-        isco_order_by_extraction(pert, yb, N, prefix, count, ord, lane);
-    } else {
-        int P2 = 1;
-        while (P2 < count) P2 <<= 1;
-        for (int k = count + lane; k < P2; k += kWave) { skey[k] = -INFINITY; sidx[k] = -1; }
-        lds_fence();
-        for (int size = 2; size <= P2; size <<= 1) {
-            for (int stride = size >> 1; stride >= 1; stride >>= 1) {
-                for (int t = lane; t < (P2 >> 1); t += kWave) {
-                    const int lo = ((t / stride) * (stride << 1)) + (t % stride);
-                    const int hi = lo + stride;
-                    const bool desc = ((lo & size) == 0);
-                    const float k0 = skey[lo], k1 = skey[hi];
-                    if ((k0 < k1) == desc) {
-                        skey[lo] = k1; skey[hi] = k0;
-                        const int t0 = sidx[lo]; sidx[lo] = sidx[hi]; sidx[hi] = t0;
-                    }
-                }
-                lds_fence();
-            }
-        }
-    }
-    auto sel_at = [&](int k) -> int { return big ? ord[k] : sidx[k]; };
-    // ---- ll_x2y: log-probability of drawing the selected set in that order (util.py:530-552)
-    const float ll_x2y = noreplacement_ll_sum(count, lmax, lane, [&](int k) { return lp[sel_at(k)]; });
-    // ---- y = x with the selected nodes flipped (env_ISCO.py:41-43)
-    for (int64_t i = lane; i < N; i += kWave) yb[i] = xb[i];
-    lds_fence();
-    for (int k = lane; k < count; k += kWave) yb[sel_at(k)] ^= 1;
-    lds_fence();
-    if (a.mask_out) {
-        for (int64_t i = lane; i < N; i += kWave) a.mask_out[b * N + i] = xb[i] ^ yb[i];
-    }
-    // ---- backward: ll_y and the probability of undoing the selection in reverse order (env_ISCO.py:65-77)
-    const float ll_y = isco_local_dist<M>(yb, lp, N, a.rowptr, a.col, a.ell_ptr, a.ell, T, a.lam, lane);
-    float bmax = -INFINITY;
-    for (int k = lane; k < count; k += kWave) bmax = fmaxf(bmax, lp[sel_at(k)]);
-    bmax = wave_max_f(bmax);
-    const float ll_y2x = noreplacement_ll_sum(count, bmax, lane, [&](int k) { return lp[sel_at(count - 1 - k)]; });
-    // ---- Metropolis-Hastings accept (env_ISCO.py:31-33, util.py:556-570)
-    const float log_acc = fminf(((ll_y + ll_y2x) - ll_x) - ll_x2y, 0.0f);
-    const float ua = a.u_accept ? a.u_accept[b] : isco_unit(isco_draw(a.seed, genv, 0xFFFFFFFFu, 0, 2));
-    const bool accept = logf(ua + 1e-24f) < log_acc;
-    float* yo = a.y_out + b * N;
-    for (int64_t i = lane; i < N; i += kWave) yo[i] = (float)(accept ? yb[i] : xb[i]);
-    if (lane == 0) {
-        if (a.energy_out) a.energy_out[b] = ll_y * T;              // the reference returns ll_y * temperature of the PROPOSAL
-        if (a.acc_out) a.acc_out[b] = expf(log_acc);
-        if (a.terms_out) {
-            float* t = a.terms_out + b * 5;
-            t[0] = ll_x; t[1] = ll_x2y; t[2] = ll_y; t[3] = ll_y2x; t[4] = log_acc;
-        }
-    }
-}
-
-// The same step with a WORKGROUP per sample, for the few-chain regime the reference's own configs run in (one chain:
-// a lone wave is instruction-issue bound, ~155 us per step on a G22-sized graph).  The node loops are split over the
-// kIscoWgWaves waves; maxima / sums meet through LDS; the L-th largest perturbed value comes from four 8-bit histogram
-// passes (LDS atomics) instead of 32 one-bit passes; the <= L selected entries are sorted and their path
-// log-probabilities summed by wave 0 as before.  Same arithmetic per element; row sums are reduced wave by wave.
-constexpr int kIscoWgWaves = 16;
-
-struct IscoWgScratch { float f[kIscoWgWaves]; int i[kIscoWgWaves]; int hist[256]; int count; uint32_t prefix; int want; };
-
-__device__ __forceinline__ float isco_block_max(float v, IscoWgScratch* sc, int lane, int w) {
-    v = wave_max_f(v);
-    __syncthreads();
-    if (lane == 0) sc->f[w] = v;
-    __syncthreads();
-    float m = sc->f[0];
-#pragma unroll
-    for (int k = 1; k < kIscoWgWaves; ++k) m = fmaxf(m, sc->f[k]);
-    return m;
-}
-__device__ __forceinline__ float isco_block_sum(float v, IscoWgScratch* sc, int lane, int w) {
-    v = wave_sum_f32x(v);
-    __syncthreads();
-    if (lane == 0) sc->f[w] = v;
-    __syncthreads();
-    float m = 0.0f;
-#pragma unroll
-    for (int k = 0; k < kIscoWgWaves; ++k) m += sc->f[k];
-    return m;
-}
-__device__ __forceinline__ int isco_block_sum_i(int v, IscoWgScratch* sc, int lane, int w) {
-    v = wave_sum_i32(v);
-    __syncthreads();
-    if (lane == 0) sc->i[w] = v;
-    __syncthreads();
-    int m = 0;
-#pragma unroll
-    for (int k = 0; k < kIscoWgWaves; ++k) m += sc->i[k];
-    return m;
-}
-
 // isco_local_dist over the whole workgroup: wave w takes the 64-node groups w, w + W, ...
 template <class M>
 __device__ __forceinline__ float isco_local_dist_wg(const uint8_t* s, float* lp, int64_t N, const IscoMcArgs& a, float temperature,
@@ -462,162 +498,38 @@ __device__ __forceinline__ float isco_local_dist_wg(const uint8_t* s, float* lp,
     return M::ll(acc, temperature, a.lam, [&](int v) { return isco_block_sum_i(v, sc, lane, w); });   // (its barriers also publish lp[])
 }
 
-// GROWS: the two f32 rows (lp, pert) live in the caller's scratch (global memory, L2-resident while a sample is worked on) and
-// LDS holds the byte rows and the list only -- N past ~15 900, up to ~81 000.  The workgroup's barriers order its global
-// stores and loads as they do the LDS ones (__syncthreads fences both at workgroup scope; the L1 is the CU's).
-template <class M, bool GROWS>
-__global__ __launch_bounds__(kIscoWgWaves * kWave) void k_isco_maxcut_step_wg(IscoMcArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int lane = threadIdx.x & (kWave - 1);
-    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
-    const int tid = threadIdx.x, NT = kIscoWgWaves * kWave;
-    const int64_t b = blockIdx.x;
-    const int64_t N = a.N;
-    const int P = a.P;
-    const size_t nb8 = ((size_t)N + 7) & ~(size_t)7;
-    uint8_t* xb = smem;
-    uint8_t* yb = smem + nb8;
-    float* lp = GROWS ? a.rows + b * 2 * N : reinterpret_cast<float*>(smem + 2 * nb8);
-    float* pert = lp + N;
-    float* skey = GROWS ? reinterpret_cast<float*>(smem + 2 * nb8) : pert + N;
-    int32_t* sidx = reinterpret_cast<int32_t*>(skey + P);
-    IscoWgScratch* sc = reinterpret_cast<IscoWgScratch*>(sidx + P);
-    const float* xr = a.x + b * N;
-    const float T = a.temperature;
-    const uint64_t genv = (uint64_t)(b + a.env_offset);
-
-    for (int64_t i = tid; i < N; i += NT) xb[i] = xr[i] > 0.0f ? 1 : 0;
-    __syncthreads();
-    // ---- forward: ll_x, proposal distribution, Gumbel perturbation
-    const float ll_x = isco_local_dist_wg<M>(xb, lp, N, a, T, sc, lane, w);
-    float lmax = -INFINITY;
-    for (int64_t i = tid; i < N; i += NT) {
-        const float u = a.u_gumbel ? a.u_gumbel[b * N + i] : isco_unit(isco_draw(a.seed, genv, (uint32_t)i, 0, 1));
-        const float l = lp[i];
-        pert[i] = l - logf(-logf(u));
-        lmax = fmaxf(lmax, l);
+// What the two step bodies below ask of a sample's source -- everything that differs between the graph steps and the dense one:
+//   Args             the kernel's argument struct (the bodies read the fields the two share by name)
+//   kWaveTie         whether the wave-per-sample body breaks ties of the sort by node id
+//   bit(i)           the input element i as a bit
+//   local_dist[_wg]  the proposal distribution of state s into lp, energy(s) / T returned, by a wave / by the workgroup
+//   after_flip       between the flip and the backward distribution (the piece t of nt of the team)
+//   ord()            where the order of a selection larger than the list lives
+//   clamp0           the clamp of the log-acceptance at 0
+//   put(i, v)        the output element i from a bit
+// Graph steps, energy model M: f32 samples, the distribution from neighbour walks.
+template <class M>
+struct IscoGraph {
+    using Args = IscoMcArgs;
+    // false: what this kernel has always computed -- its compaction is in node order, only the sort's own order of equal keys differs
+    static constexpr bool kWaveTie = false;
+    const IscoMcArgs& a;
+    const float* xr;
+    float* yo;
+    __device__ __forceinline__ IscoGraph(const IscoMcArgs& a_, int64_t b) : a(a_), xr(a_.x + b * a_.N), yo(a_.y_out + b * a_.N) {}
+    __device__ __forceinline__ bool bit(int64_t i) const { return xr[i] > 0.0f; }
+    __device__ __forceinline__ float local_dist(const uint8_t* s, float* lp, int lane) const {
+        return isco_local_dist<M>(s, lp, a.N, a.rowptr, a.col, a.ell_ptr, a.ell, a.temperature, a.lam, lane);
     }
-    lmax = isco_block_max(lmax, sc, lane, w);                  // ll_base of the forward renormalisation (also publishes pert[])
-    // ---- threshold = L-th largest perturbed value: radix select, 8 bits per pass
-    int64_t L = a.path_length[b];
-    L = L < 1 ? 1 : (L > N ? N : L);
-    uint32_t prefix = 0;
-    int want = (int)L;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        const uint32_t hi_mask = shift == 24 ? 0u : (0xFFFFFFFFu << (shift + 8));
-        for (int k = tid; k < 256; k += NT) sc->hist[k] = 0;
-        __syncthreads();
-        for (int64_t i = tid; i < N; i += NT) {
-            const uint32_t k = fkey(pert[i]);
-            if ((k & hi_mask) == prefix) atomicAdd(&sc->hist[(k >> shift) & 255u], 1);
-        }
-        __syncthreads();
-        if (w == 0) {   // the largest byte value v whose suffix count (entries with byte >= v) reaches `want`
-            int c[4], tot = 0;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { c[q] = sc->hist[lane * 4 + q]; tot += c[q]; }
-            int suf = tot;                                        // inclusive suffix sum over lanes: lanes >= this one
-#pragma unroll
-            for (int d = 1; d < kWave; d <<= 1) {
-                const int o = __shfl_down(suf, d, 64);
-                if (lane + d < kWave) suf += o;
-            }
-            const int above = suf - tot;                          // entries in bins of higher lanes
-            // inside this lane's four bins, from the top
-            int byte_found = -1, want_left = 0, run = above;
-#pragma unroll
-            for (int q = 3; q >= 0; --q) {
-                if (byte_found < 0 && run < want && run + c[q] >= want) { byte_found = lane * 4 + q; want_left = want - run; }
-                run += c[q];
-            }
-            const uint64_t m = ballot64(byte_found >= 0);
-            if (byte_found >= 0) { sc->prefix = prefix | ((uint32_t)byte_found << shift); sc->want = want_left; }
-            (void)m;
-        }
-        __syncthreads();
-        prefix = sc->prefix;
-        want = sc->want;
+    __device__ __forceinline__ float local_dist_wg(const uint8_t* s, float* lp, IscoWgScratch* sc, int lane, int w, int) const {
+        return isco_local_dist_wg<M>(s, lp, a.N, a, a.temperature, sc, lane, w);
     }
-    // ---- selected set (perturbed >= threshold), compacted (any order: sorted next)
-    if (tid == 0) sc->count = 0;
-    __syncthreads();
-    for (int64_t i = tid; i < N; i += NT) {
-        if (fkey(pert[i]) >= prefix) {
-            const int at = atomicAdd(&sc->count, 1);
-            if (at < P) {
-                skey[at] = pert[i];
-                sidx[at] = (int)i;
-            }
-        }
-    }
-    __syncthreads();
-    const int count = sc->count;
-    const bool big = count > P;                                  // the list does not hold the selection: order by extraction
-    int32_t* ord = reinterpret_cast<int32_t*>(a.y_out + b * N);  // (this sample's output row, written last)
-    auto sel_at = [&](int k) -> int { return big ? ord[k] : sidx[k]; };
-    float ll_x2y = 0.0f;
-    if (w == 0 && big) {
-        isco_order_by_extraction(pert, yb, N, prefix, count, ord, lane);
-        ll_x2y = noreplacement_ll_sum(count, lmax, lane, [&](int k) { return lp[ord[k]]; });
-    } else if (w == 0) {
-        int P2 = 1;
-        while (P2 < count) P2 <<= 1;
-        for (int k = count + lane; k < P2; k += kWave) { skey[k] = -INFINITY; sidx[k] = -1; }
-        lds_fence();
-        for (int size = 2; size <= P2; size <<= 1) {
-            for (int stride = size >> 1; stride >= 1; stride >>= 1) {
-                for (int t = lane; t < (P2 >> 1); t += kWave) {
-                    const int lo = ((t / stride) * (stride << 1)) + (t % stride);
-                    const int hi = lo + stride;
-                    const bool desc = ((lo & size) == 0);
-                    const float k0 = skey[lo], k1 = skey[hi];
-                    // equal keys: order by node id, so that the result does not depend on the compaction order
-                    const int i0 = sidx[lo], i1 = sidx[hi];
-                    const bool lt = (k0 < k1) || (k0 == k1 && i0 > i1);
-                    if (lt == desc) {
-                        skey[lo] = k1; skey[hi] = k0;
-                        sidx[lo] = i1; sidx[hi] = i0;
-                    }
-                }
-                lds_fence();
-            }
-        }
-        ll_x2y = noreplacement_ll_sum(count, lmax, lane, [&](int k) { return lp[sidx[k]]; });
-    }
-    // ---- y = x with the selected nodes flipped
-    __syncthreads();                                              // (wave 0 may have used yb as the extraction's marks)
-    for (int64_t i = tid; i < N; i += NT) yb[i] = xb[i];
-    __syncthreads();
-    for (int k = tid; k < count; k += NT) yb[sel_at(k)] ^= 1;
-    __syncthreads();
-    if (a.mask_out) {
-        for (int64_t i = tid; i < N; i += NT) a.mask_out[b * N + i] = xb[i] ^ yb[i];
-    }
-    // ---- backward
-    const float ll_y = isco_local_dist_wg<M>(yb, lp, N, a, T, sc, lane, w);
-    if (w == 0) {
-        float bmax = -INFINITY;
-        for (int k = lane; k < count; k += kWave) bmax = fmaxf(bmax, lp[sel_at(k)]);
-        bmax = wave_max_f(bmax);
-        const float ll_y2x = noreplacement_ll_sum(count, bmax, lane, [&](int k) { return lp[sel_at(count - 1 - k)]; });
-        const float log_acc = fminf(((ll_y + ll_y2x) - ll_x) - ll_x2y, 0.0f);
-        const float ua = a.u_accept ? a.u_accept[b] : isco_unit(isco_draw(a.seed, genv, 0xFFFFFFFFu, 0, 2));
-        const bool accept = logf(ua + 1e-24f) < log_acc;
-        if (lane == 0) {
-            sc->want = accept ? 1 : 0;
-            if (a.energy_out) a.energy_out[b] = ll_y * T;
-            if (a.acc_out) a.acc_out[b] = expf(log_acc);
-            if (a.terms_out) {
-                float* t = a.terms_out + b * 5;
-                t[0] = ll_x; t[1] = ll_x2y; t[2] = ll_y; t[3] = ll_y2x; t[4] = log_acc;
-            }
-        }
-    }
-    __syncthreads();
-    const bool accept = sc->want != 0;
-    float* yo = a.y_out + b * N;
-    for (int64_t i = tid; i < N; i += NT) yo[i] = (float)(accept ? yb[i] : xb[i]);
-}
+    template <typename S>
+    __device__ __forceinline__ void after_flip(float*, const uint8_t*, int, S, int, int) {}
+    __device__ __forceinline__ int32_t* ord() const { return reinterpret_cast<int32_t*>(yo); }   // this sample's output row, written last
+    __device__ static __forceinline__ float clamp0(float v) { return fminf(v, 0.0f); }
+    __device__ __forceinline__ void put(int64_t i, uint8_t v) const { yo[i] = (float)v; }
+};
 
 // ----------------------------------------------------------------------------------------------- PISCO (dense, weighted MaxCut)
 // PISCO_maxcut.step (env_ISCO.py:384-434): the MaxCut step with the local distribution of a sample read from its row of the
@@ -626,7 +538,6 @@ __global__ __launch_bounds__(kIscoWgWaves * kWave) void k_isco_maxcut_step_wg(Is
 // The proposal's row is the rank-L update r'_j = r_j - 2 sum_{k selected} delta_k A[k][j] (delta of x; contiguous f16 rows of the
 // symmetric A), so a step runs one product.  half_rounding: r and sum_k r_k delta_k each rounded to f16 once, as the reference's
 // half matmul and half sum do.  Samples are f16 in and out; all Np columns -- the padded ones too -- take part.
-// These kernels are copies of the two above, not further instantiations of them: the graph models keep their code as it was.
 struct PiscoArgs {
     const uint16_t* adj; int64_t N;                       // f16 [N, N], N % 8 == 0
     const uint16_t* x; uint16_t* y_out; int64_t B;        // f16 [B, N]
@@ -693,149 +604,6 @@ __device__ __forceinline__ float pisco_local_dist(const uint8_t* s, const float*
     return pisco_energy(wave_sum_f32x(sum), temperature, half);
 }
 
-__global__ __launch_bounds__(512) void k_pisco_step(PiscoArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wib = threadIdx.x / kWave;
-    const int64_t b = (int64_t)blockIdx.x * (blockDim.x / kWave) + wib;
-    if (b >= a.B) return;
-    const int64_t N = a.N;
-    const int P = a.P;
-    const size_t per_wave = 2 * (size_t)N + (size_t)N * 8 + (size_t)P * 8;
-    unsigned char* base = smem + (size_t)wib * per_wave;
-    uint8_t* xb = base;
-    uint8_t* yb = base + N;
-    float* lp = reinterpret_cast<float*>(base + 2 * N);
-    float* pert = lp + N;
-    float* skey = pert + N;
-    int32_t* sidx = reinterpret_cast<int32_t*>(skey + P);
-    const uint16_t* xr = a.x + b * N;
-    const float* rrow = a.r + b * N;
-    const float T = a.temperature;
-    const bool half = a.half_rounding != 0;
-    const uint64_t genv = (uint64_t)(b + a.env_offset);
-
-    for (int64_t i = lane; i < N; i += kWave) xb[i] = pisco_is_set(xr[i]) ? 1 : 0;
-    lds_fence();
-    // ---- forward: ll_x, proposal distribution, Gumbel perturbation (env_ISCO.py:407-416, util.py:498-516)
-    const float ll_x = pisco_local_dist(xb, rrow, lp, N, T, half, lane);
-    float lmax = -INFINITY;
-    for (int64_t i = lane; i < N; i += kWave) {
-        const float u = a.u_gumbel ? a.u_gumbel[b * N + i] : isco_unit(isco_draw(a.seed, genv, (uint32_t)i, 0, 1));
-        const float l = lp[i];
-        pert[i] = l - logf(-logf(u));
-        lmax = fmaxf(lmax, l);
-    }
-    lmax = wave_max_f(lmax);
-    lds_fence();
-    // ---- threshold = L-th largest perturbed value: radix select on the monotone key
-    int64_t L = a.path_length[b];
-    L = L < 1 ? 1 : (L > N ? N : L);
-    uint32_t prefix = 0;
-    int want = (int)L;
-    if (N <= 32 * kWave) {
-        uint32_t kk[32];
-#pragma unroll
-        for (int j = 0; j < 32; ++j) {
-            const int64_t i = lane + (int64_t)j * kWave;
-            kk[j] = i < N ? fkey(pert[i]) : 0u;
-        }
-        for (int bit = 31; bit >= 0; --bit) {
-            const uint32_t hi_mask = bit == 31 ? 0u : (0xFFFFFFFFu << (bit + 1));
-            int cnt = 0;
-#pragma unroll
-            for (int j = 0; j < 32; ++j) cnt += ((kk[j] & hi_mask) == prefix) && ((kk[j] >> bit) & 1u);
-            cnt = wave_sum_i32(cnt);
-            if (cnt >= want) prefix |= 1u << bit;
-            else want -= cnt;
-        }
-    } else {
-        for (int bit = 31; bit >= 0; --bit) {
-            const uint32_t hi_mask = bit == 31 ? 0u : (0xFFFFFFFFu << (bit + 1));
-            int cnt = 0;
-            for (int64_t i = lane; i < N; i += kWave) {
-                const uint32_t k = fkey(pert[i]);
-                cnt += ((k & hi_mask) == prefix) && ((k >> bit) & 1u);
-            }
-            cnt = wave_sum_i32(cnt);
-            if (cnt >= want) prefix |= 1u << bit;
-            else want -= cnt;
-        }
-    }
-    // ---- selected set, compacted then sorted by perturbed value, descending
-    int count = 0;
-    for (int64_t i0 = 0; i0 < N; i0 += kWave) {
-        const int64_t i = i0 + lane;
-        const bool sel = i < N && fkey(pert[i]) >= prefix;
-        const uint64_t m = ballot64(sel);
-        if (sel) {
-            const int at = count + __popcll(m & ((1ull << lane) - 1ull));
-            if (at < P) {
-                skey[at] = pert[i];
-                sidx[at] = (int)i;
-            }
-        }
-        count += __popcll(m);
-    }
-    const bool big = count > P;
-    int32_t* ord = a.ord + b * N;                                // an f16 output row is too short for it: the caller's scratch
-    if (big) {
-        isco_order_by_extraction(pert, yb, N, prefix, count, ord, lane);
-    } else {
-        int P2 = 1;
-        while (P2 < count) P2 <<= 1;
-        for (int k = count + lane; k < P2; k += kWave) { skey[k] = -INFINITY; sidx[k] = -1; }
-        lds_fence();
-        for (int size = 2; size <= P2; size <<= 1) {
-            for (int stride = size >> 1; stride >= 1; stride >>= 1) {
-                for (int t = lane; t < (P2 >> 1); t += kWave) {
-                    const int lo = ((t / stride) * (stride << 1)) + (t % stride);
-                    const int hi = lo + stride;
-                    const bool desc = ((lo & size) == 0);
-                    const float k0 = skey[lo], k1 = skey[hi];
-                    const int i0 = sidx[lo], i1 = sidx[hi];
-                    const bool lt = (k0 < k1) || (k0 == k1 && i0 > i1);      // equal keys: lowest node first, as the extraction
-                    if (lt == desc) {
-                        skey[lo] = k1; skey[hi] = k0;
-                        sidx[lo] = i1; sidx[hi] = i0;
-                    }
-                }
-                lds_fence();
-            }
-        }
-    }
-    auto sel_at = [&](int k) -> int { return big ? ord[k] : sidx[k]; };
-    const float ll_x2y = noreplacement_ll_sum(count, lmax, lane, [&](int k) { return lp[sel_at(k)]; });
-    // ---- y = x with the selected columns flipped; its row of the product by the rank-L update, into pert (free from here on)
-    for (int64_t i = lane; i < N; i += kWave) yb[i] = xb[i];
-    lds_fence();
-    for (int k = lane; k < count; k += kWave) yb[sel_at(k)] ^= 1;
-    pisco_rank_update(a, rrow, pert, xb, count, sel_at, lane, kWave);
-    lds_fence();
-    if (a.mask_out) {
-        for (int64_t i = lane; i < N; i += kWave) a.mask_out[b * N + i] = xb[i] ^ yb[i];
-    }
-    // ---- backward
-    const float ll_y = pisco_local_dist(yb, pert, lp, N, T, half, lane);
-    float bmax = -INFINITY;
-    for (int k = lane; k < count; k += kWave) bmax = fmaxf(bmax, lp[sel_at(k)]);
-    bmax = wave_max_f(bmax);
-    const float ll_y2x = noreplacement_ll_sum(count, bmax, lane, [&](int k) { return lp[sel_at(count - 1 - k)]; });
-    const float log_acc = pisco_clamp0(((ll_y + ll_y2x) - ll_x) - ll_x2y);
-    const float ua = a.u_accept ? a.u_accept[b] : isco_unit(isco_draw(a.seed, genv, 0xFFFFFFFFu, 0, 2));
-    const bool accept = logf(ua + 1e-24f) < log_acc;
-    uint16_t* yo = a.y_out + b * N;
-    for (int64_t i = lane; i < N; i += kWave) yo[i] = (accept ? yb[i] : xb[i]) ? 0x3C00 : 0;
-    if (lane == 0) {
-        if (a.energy_out) a.energy_out[b] = ll_y * T;
-        if (a.acc_out) a.acc_out[b] = expf(log_acc);
-        if (a.terms_out) {
-            float* t = a.terms_out + b * 5;
-            t[0] = ll_x; t[1] = ll_x2y; t[2] = ll_y; t[3] = ll_y2x; t[4] = log_acc;
-        }
-    }
-}
-
 __device__ __forceinline__ float pisco_local_dist_wg(const uint8_t* s, const float* rrow, float* lp, int64_t N, float temperature,
                                                      bool half, IscoWgScratch* sc, int lane, int w, int tid) {
     constexpr int NT = kIscoWgWaves * kWave;
@@ -849,7 +617,111 @@ __device__ __forceinline__ float pisco_local_dist_wg(const uint8_t* s, const flo
     return pisco_energy(isco_block_sum(sum, sc, lane, w), temperature, half);      // (its barriers also publish lp[])
 }
 
-__global__ __launch_bounds__(kIscoWgWaves * kWave) void k_pisco_step_wg(PiscoArgs a) {
+// The dense step's source: f16 samples, the distribution from `row` -- the sample's row of the product, then (after the flip)
+// the proposal's row, which the rank-L update leaves in pert[] (free from there on).
+struct IscoDense {
+    using Args = PiscoArgs;
+    static constexpr bool kWaveTie = true;
+    const PiscoArgs& a;
+    const uint16_t* xr;
+    uint16_t* yo;
+    const float* row;
+    const bool half;
+    int32_t* const ordp;
+    __device__ __forceinline__ IscoDense(const PiscoArgs& a_, int64_t b)
+        : a(a_), xr(a_.x + b * a_.N), yo(a_.y_out + b * a_.N), row(a_.r + b * a_.N), half(a_.half_rounding != 0), ordp(a_.ord + b * a_.N) {}
+    __device__ __forceinline__ bool bit(int64_t i) const { return pisco_is_set(xr[i]); }
+    __device__ __forceinline__ float local_dist(const uint8_t* s, float* lp, int lane) const {
+        return pisco_local_dist(s, row, lp, a.N, a.temperature, half, lane);
+    }
+    __device__ __forceinline__ float local_dist_wg(const uint8_t* s, float* lp, IscoWgScratch* sc, int lane, int w, int tid) const {
+        return pisco_local_dist_wg(s, row, lp, a.N, a.temperature, half, sc, lane, w, tid);
+    }
+    template <typename S>
+    __device__ __forceinline__ void after_flip(float* pert, const uint8_t* xb, int count, S sel_at, int t, int nt) {
+        pisco_rank_update(a, row, pert, xb, count, sel_at, t, nt);
+        row = pert;
+    }
+    __device__ __forceinline__ int32_t* ord() const { return ordp; }   // an f16 output row is too short for it: the caller's scratch
+    __device__ static __forceinline__ float clamp0(float v) { return pisco_clamp0(v); }
+    __device__ __forceinline__ void put(int64_t i, uint8_t v) const { yo[i] = v ? 0x3C00 : 0; }
+};
+
+// ----------------------------------------------------------------------------------------------- the two step bodies
+// A WAVE per sample, its rows in this wave's slice of LDS.
+template <class S>
+__device__ __forceinline__ void isco_step_wave(const typename S::Args& a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wib = threadIdx.x / kWave;
+    const int64_t b = (int64_t)blockIdx.x * (blockDim.x / kWave) + wib;
+    if (b >= a.B) return;
+    const int64_t N = a.N;
+    const int P = a.P;
+    const size_t nb8 = ((size_t)N + 7) & ~(size_t)7;
+    const size_t per_wave = 2 * nb8 + (size_t)N * 8 + (size_t)P * 8;
+    unsigned char* base = smem + (size_t)wib * per_wave;
+    uint8_t* xb = base;
+    uint8_t* yb = base + nb8;
+    float* lp = reinterpret_cast<float*>(base + 2 * nb8);
+    float* pert = lp + N;
+    float* skey = pert + N;
+    int32_t* sidx = reinterpret_cast<int32_t*>(skey + P);
+    const uint64_t genv = (uint64_t)(b + a.env_offset);
+    S src(a, b);
+
+    for (int64_t i = lane; i < N; i += kWave) xb[i] = src.bit(i) ? 1 : 0;
+    lds_fence();
+    // ---- forward: ll_x, proposal distribution, Gumbel perturbation (env_ISCO.py:51-63, util.py:498-516)
+    const float ll_x = src.local_dist(xb, lp, lane);
+    float lmax = -INFINITY;
+    for (int64_t i = lane; i < N; i += kWave) {
+        const float u = a.u_gumbel ? a.u_gumbel[b * N + i] : isco_unit(isco_draw(a.seed, genv, (uint32_t)i, 0, 1));
+        const float l = lp[i];
+        pert[i] = l - logf(-logf(u));
+        lmax = fmaxf(lmax, l);
+    }
+    lmax = wave_max_f(lmax);                                   // ll_base of the forward renormalisation: max over ALL entries
+    lds_fence();
+    // ---- the selected set: perturbed >= the L-th largest perturbed value, compacted then sorted by perturbed value, descending
+    int64_t L = a.path_length[b];
+    L = L < 1 ? 1 : (L > N ? N : L);
+    const uint32_t prefix = isco_threshold_wave(pert, N, (int)L, lane);
+    const int count = isco_compact_wave(pert, N, prefix, skey, sidx, P, lane);
+    const bool big = count > P;                                  // (wave-uniform) the list does not hold the selection
+    int32_t* ord = src.ord();                                    // its order then lives there until the end
+    if (big) isco_order_by_extraction(pert, yb, N, prefix, count, ord, lane);
+    else isco_sort_list<S::kWaveTie>(skey, sidx, count, lane);   // (graph steps: no tie-break, as ever -- see IscoGraph::kWaveTie)
+    auto sel_at = [&](int k) -> int { return big ? ord[k] : sidx[k]; };
+    // ---- ll_x2y: log-probability of drawing the selected set in that order (util.py:530-552)
+    const float ll_x2y = noreplacement_ll_sum(count, lmax, lane, [&](int k) { return lp[sel_at(k)]; });
+    // ---- y = x with the selected nodes flipped (env_ISCO.py:41-43)
+    for (int64_t i = lane; i < N; i += kWave) yb[i] = xb[i];
+    lds_fence();
+    for (int k = lane; k < count; k += kWave) yb[sel_at(k)] ^= 1;
+    src.after_flip(pert, xb, count, sel_at, lane, kWave);
+    lds_fence();
+    if (a.mask_out) {
+        for (int64_t i = lane; i < N; i += kWave) a.mask_out[b * N + i] = xb[i] ^ yb[i];
+    }
+    // ---- backward: ll_y and the probability of undoing the selection in reverse order (env_ISCO.py:65-77)
+    const float ll_y = src.local_dist(yb, lp, lane);
+    const float ll_y2x = isco_reverse_ll(lp, count, sel_at, lane);
+    const float log_acc = S::clamp0(((ll_y + ll_y2x) - ll_x) - ll_x2y);
+    const bool accept = isco_mh_accept(a, b, ll_x, ll_x2y, ll_y, ll_y2x, log_acc, lane);
+    for (int64_t i = lane; i < N; i += kWave) src.put(i, accept ? yb[i] : xb[i]);
+}
+
+// The same step with a WORKGROUP per sample, for the few-chain regime the reference's own configs run in (one chain:
+// a lone wave is instruction-issue bound, ~155 us per step on a G22-sized graph).  The node loops are split over the
+// kIscoWgWaves waves; maxima / sums meet through LDS; the L-th largest perturbed value comes from four 8-bit histogram
+// passes (LDS atomics) instead of 32 one-bit passes; the <= L selected entries are sorted and their path
+// log-probabilities summed by wave 0 as before.  Same arithmetic per element; row sums are reduced wave by wave.
+// GROWS: the two f32 rows (lp, pert) live in the caller's scratch (global memory, L2-resident while a sample is worked on) and
+// LDS holds the byte rows and the list only -- N past ~15 900, up to ~81 000.  The workgroup's barriers order its global
+// stores and loads as they do the LDS ones (__syncthreads fences both at workgroup scope; the L1 is the CU's).
+template <class S, bool GROWS>
+__device__ __forceinline__ void isco_step_wg(const typename S::Args& a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & (kWave - 1);
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
@@ -857,22 +729,23 @@ __global__ __launch_bounds__(kIscoWgWaves * kWave) void k_pisco_step_wg(PiscoArg
     const int64_t b = blockIdx.x;
     const int64_t N = a.N;
     const int P = a.P;
+    const size_t nb8 = ((size_t)N + 7) & ~(size_t)7;
     uint8_t* xb = smem;
-    uint8_t* yb = smem + N;
-    float* lp = reinterpret_cast<float*>(smem + 2 * N);
+    uint8_t* yb = smem + nb8;
+    float* lp;
+    if constexpr (GROWS) lp = a.rows + b * 2 * N;
+    else lp = reinterpret_cast<float*>(smem + 2 * nb8);
     float* pert = lp + N;
-    float* skey = pert + N;
+    float* skey = GROWS ? reinterpret_cast<float*>(smem + 2 * nb8) : pert + N;
     int32_t* sidx = reinterpret_cast<int32_t*>(skey + P);
     IscoWgScratch* sc = reinterpret_cast<IscoWgScratch*>(sidx + P);
-    const uint16_t* xr = a.x + b * N;
-    const float* rrow = a.r + b * N;
-    const float T = a.temperature;
-    const bool half = a.half_rounding != 0;
     const uint64_t genv = (uint64_t)(b + a.env_offset);
+    S src(a, b);
 
-    for (int64_t i = tid; i < N; i += NT) xb[i] = pisco_is_set(xr[i]) ? 1 : 0;
+    for (int64_t i = tid; i < N; i += NT) xb[i] = src.bit(i) ? 1 : 0;
     __syncthreads();
-    const float ll_x = pisco_local_dist_wg(xb, rrow, lp, N, T, half, sc, lane, w, tid);
+    // ---- forward: ll_x, proposal distribution, Gumbel perturbation
+    const float ll_x = src.local_dist_wg(xb, lp, sc, lane, w, tid);
     float lmax = -INFINITY;
     for (int64_t i = tid; i < N; i += NT) {
         const float u = a.u_gumbel ? a.u_gumbel[b * N + i] : isco_unit(isco_draw(a.seed, genv, (uint32_t)i, 0, 1));
@@ -880,122 +753,52 @@ __global__ __launch_bounds__(kIscoWgWaves * kWave) void k_pisco_step_wg(PiscoArg
         pert[i] = l - logf(-logf(u));
         lmax = fmaxf(lmax, l);
     }
-    lmax = isco_block_max(lmax, sc, lane, w);
+    lmax = isco_block_max(lmax, sc, lane, w);                  // ll_base of the forward renormalisation (also publishes pert[])
+    // ---- the selected set: perturbed >= the L-th largest perturbed value, compacted, then ordered by wave 0
     int64_t L = a.path_length[b];
     L = L < 1 ? 1 : (L > N ? N : L);
-    uint32_t prefix = 0;
-    int want = (int)L;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        const uint32_t hi_mask = shift == 24 ? 0u : (0xFFFFFFFFu << (shift + 8));
-        for (int k = tid; k < 256; k += NT) sc->hist[k] = 0;
-        __syncthreads();
-        for (int64_t i = tid; i < N; i += NT) {
-            const uint32_t k = fkey(pert[i]);
-            if ((k & hi_mask) == prefix) atomicAdd(&sc->hist[(k >> shift) & 255u], 1);
-        }
-        __syncthreads();
-        if (w == 0) {
-            int c[4], tot = 0;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { c[q] = sc->hist[lane * 4 + q]; tot += c[q]; }
-            int suf = tot;
-#pragma unroll
-            for (int d = 1; d < kWave; d <<= 1) {
-                const int o = __shfl_down(suf, d, 64);
-                if (lane + d < kWave) suf += o;
-            }
-            const int above = suf - tot;
-            int byte_found = -1, want_left = 0, run = above;
-#pragma unroll
-            for (int q = 3; q >= 0; --q) {
-                if (byte_found < 0 && run < want && run + c[q] >= want) { byte_found = lane * 4 + q; want_left = want - run; }
-                run += c[q];
-            }
-            if (byte_found >= 0) { sc->prefix = prefix | ((uint32_t)byte_found << shift); sc->want = want_left; }
-        }
-        __syncthreads();
-        prefix = sc->prefix;
-        want = sc->want;
-    }
-    if (tid == 0) sc->count = 0;
-    __syncthreads();
-    for (int64_t i = tid; i < N; i += NT) {
-        if (fkey(pert[i]) >= prefix) {
-            const int at = atomicAdd(&sc->count, 1);
-            if (at < P) {
-                skey[at] = pert[i];
-                sidx[at] = (int)i;
-            }
-        }
-    }
-    __syncthreads();
-    const int count = sc->count;
-    const bool big = count > P;
-    int32_t* ord = a.ord + b * N;
+    const uint32_t prefix = isco_threshold_wg(pert, N, (int)L, sc, lane, w, tid);
+    const int count = isco_compact_wg(pert, N, prefix, skey, sidx, P, sc, tid);
+    const bool big = count > P;                                  // the list does not hold the selection: order by extraction
+    int32_t* ord = src.ord();
     auto sel_at = [&](int k) -> int { return big ? ord[k] : sidx[k]; };
     float ll_x2y = 0.0f;
     if (w == 0 && big) {
         isco_order_by_extraction(pert, yb, N, prefix, count, ord, lane);
         ll_x2y = noreplacement_ll_sum(count, lmax, lane, [&](int k) { return lp[ord[k]]; });
     } else if (w == 0) {
-        int P2 = 1;
-        while (P2 < count) P2 <<= 1;
-        for (int k = count + lane; k < P2; k += kWave) { skey[k] = -INFINITY; sidx[k] = -1; }
-        lds_fence();
-        for (int size = 2; size <= P2; size <<= 1) {
-            for (int stride = size >> 1; stride >= 1; stride >>= 1) {
-                for (int t = lane; t < (P2 >> 1); t += kWave) {
-                    const int lo = ((t / stride) * (stride << 1)) + (t % stride);
-                    const int hi = lo + stride;
-                    const bool desc = ((lo & size) == 0);
-                    const float k0 = skey[lo], k1 = skey[hi];
-                    const int i0 = sidx[lo], i1 = sidx[hi];
-                    const bool lt = (k0 < k1) || (k0 == k1 && i0 > i1);
-                    if (lt == desc) {
-                        skey[lo] = k1; skey[hi] = k0;
-                        sidx[lo] = i1; sidx[hi] = i0;
-                    }
-                }
-                lds_fence();
-            }
-        }
+        isco_sort_list<true>(skey, sidx, count, lane);
         ll_x2y = noreplacement_ll_sum(count, lmax, lane, [&](int k) { return lp[sidx[k]]; });
     }
-    // ---- y = x with the selected columns flipped; its row of the product by the rank-L update, into pert (free from here on)
-    __syncthreads();
+    // ---- y = x with the selected nodes flipped
+    __syncthreads();                                              // (wave 0 may have used yb as the extraction's marks)
     for (int64_t i = tid; i < N; i += NT) yb[i] = xb[i];
     __syncthreads();
     for (int k = tid; k < count; k += NT) yb[sel_at(k)] ^= 1;
-    pisco_rank_update(a, rrow, pert, xb, count, sel_at, tid, NT);
+    src.after_flip(pert, xb, count, sel_at, tid, NT);
     __syncthreads();
     if (a.mask_out) {
         for (int64_t i = tid; i < N; i += NT) a.mask_out[b * N + i] = xb[i] ^ yb[i];
     }
-    // ---- backward
-    const float ll_y = pisco_local_dist_wg(yb, pert, lp, N, T, half, sc, lane, w, tid);
+    // ---- backward, the accept by wave 0
+    const float ll_y = src.local_dist_wg(yb, lp, sc, lane, w, tid);
     if (w == 0) {
-        float bmax = -INFINITY;
-        for (int k = lane; k < count; k += kWave) bmax = fmaxf(bmax, lp[sel_at(k)]);
-        bmax = wave_max_f(bmax);
-        const float ll_y2x = noreplacement_ll_sum(count, bmax, lane, [&](int k) { return lp[sel_at(count - 1 - k)]; });
-        const float log_acc = pisco_clamp0(((ll_y + ll_y2x) - ll_x) - ll_x2y);
-        const float ua = a.u_accept ? a.u_accept[b] : isco_unit(isco_draw(a.seed, genv, 0xFFFFFFFFu, 0, 2));
-        const bool accept = logf(ua + 1e-24f) < log_acc;
-        if (lane == 0) {
-            sc->want = accept ? 1 : 0;
-            if (a.energy_out) a.energy_out[b] = ll_y * T;
-            if (a.acc_out) a.acc_out[b] = expf(log_acc);
-            if (a.terms_out) {
-                float* t = a.terms_out + b * 5;
-                t[0] = ll_x; t[1] = ll_x2y; t[2] = ll_y; t[3] = ll_y2x; t[4] = log_acc;
-            }
-        }
+        const float ll_y2x = isco_reverse_ll(lp, count, sel_at, lane);
+        const float log_acc = S::clamp0(((ll_y + ll_y2x) - ll_x) - ll_x2y);
+        const bool accept = isco_mh_accept(a, b, ll_x, ll_x2y, ll_y, ll_y2x, log_acc, lane);
+        if (lane == 0) sc->want = accept ? 1 : 0;
     }
     __syncthreads();
     const bool accept = sc->want != 0;
-    uint16_t* yo = a.y_out + b * N;
-    for (int64_t i = tid; i < N; i += NT) yo[i] = (accept ? yb[i] : xb[i]) ? 0x3C00 : 0;
+    for (int64_t i = tid; i < N; i += NT) src.put(i, accept ? yb[i] : xb[i]);
 }
+
+template <class M>
+__global__ __launch_bounds__(512) void k_isco_maxcut_step(IscoMcArgs a) { isco_step_wave<IscoGraph<M>>(a); }
+template <class M, bool GROWS>
+__global__ __launch_bounds__(kIscoWgWaves * kWave) void k_isco_maxcut_step_wg(IscoMcArgs a) { isco_step_wg<IscoGraph<M>, GROWS>(a); }
+__global__ __launch_bounds__(512) void k_pisco_step(PiscoArgs a) { isco_step_wave<IscoDense>(a); }
+__global__ __launch_bounds__(kIscoWgWaves * kWave) void k_pisco_step_wg(PiscoArgs a) { isco_step_wg<IscoDense, false>(a); }
 
 // ----------------------------------------------------------------------------------------------- TSP
 struct IscoTspArgs {
@@ -1169,20 +972,16 @@ using namespace rls;
 
 extern "C" {
 
-// bytes of LDS a sample needs with its two f32 rows in LDS and the smallest list (64 entries)
-static inline size_t isco_mc_lds_min(int64_t N) {
-    return 2 * (((size_t)N + 7) & ~(size_t)7) + (size_t)N * 8 + 64 * 8 + sizeof(IscoWgScratch) + 16;
-}
-
 int64_t rls_isco_maxcut_scratch_bytes(const rls_graph* g, int64_t B) {
-    if (!g || B <= 0 || (isco_mc_lds_min(g->num_nodes) <= (size_t)kLdsBytes && !knob_on(KN_ISCO_GLOBAL_ROWS))) return 0;
+    if (!g || B <= 0 || (isco_rows_fit_lds(isco_rows_bytes(g->num_nodes)) && !knob_on(KN_ISCO_GLOBAL_ROWS))) return 0;
     return B * g->num_nodes * 8;
 }
 
 }  // extern "C"
 
-// One launcher for every energy model M of the step: validation, the list's capacity, wave vs workgroup per sample, rows in
-// LDS or in scratch -- none of it depends on the model (the rows and the lists are the same).
+// One launcher for every energy model M of the step: validation, then what isco_plan_step answers (rls_isco_plan.h: the list's
+// capacity, wave vs workgroup per sample, rows in LDS or in scratch) -- none of it depends on the model (the rows and the lists
+// are the same).
 template <class M>
 static int isco_step_launch(const rls_graph* g, const float* x, float* y_out, int64_t B, const int64_t* path_length,
                             float temperature, float lam, const float* u_gumbel, const float* u_accept, uint64_t seed,
@@ -1196,76 +995,29 @@ static int isco_step_launch(const rls_graph* g, const float* x, float* y_out, in
     RLS_REQUIRE(temperature > 0.0f, RLS_EINVAL, "temperature must be > 0");
     const int64_t N = g->num_nodes;
     RLS_REQUIRE((const void*)x != (const void*)y_out, RLS_EINVAL, "y_out must not alias x (a rejected proposal restores x; the row also serves as scratch)");
-    // capacity of the selected-set list in LDS: a power of two >= N while that fits (N <= 4096: as before), else the largest
-    // power of two the rows leave room for, at least 64 (N = 10^4: 4096; N = 15 000: 512) -- a larger selection takes the
-    // extraction path.  The rows themselves (two byte rows, two f32 rows) bound N at ~15 900.
-    const int force_cap = (int)knob(KN_ISCO_SEL_CAP, 0);   // dev / test knob
-    const size_t fixed = sizeof(IscoWgScratch) + 16;
-    const bool use_ell = g->ell_sym_ptr && g->ell_sym && !g->wgt;
-    if (isco_mc_lds_min(N) > (size_t)kLdsBytes || knob_on(KN_ISCO_GLOBAL_ROWS)) {
-        // rows past the LDS: a workgroup per sample with lp / pert in the caller's scratch (rls_isco_maxcut_scratch_bytes), the byte
-        // rows and a list of up to 4096 entries in LDS
-        const size_t brow = 2 * (((size_t)N + 7) & ~(size_t)7);
-        RLS_REQUIRE(brow + 64 * 8 + fixed <= (size_t)kLdsBytes, RLS_EUNSUPPORTED, "N=%lld: the two byte rows of a sample need %zu B of LDS (max %d)",
-                    (long long)N, brow + 64 * 8 + fixed, kLdsBytes);
+    const IscoPlan p = isco_plan_step(isco_rows_bytes(N), N, B, num_cus(), 1, true);
+    RLS_REQUIRE(p.err == RLS_OK, p.err, "N=%lld: the two byte rows of a sample need %zu B of LDS (max %d)", (long long)N, p.need, kLdsBytes);
+    if (p.grows)
         RLS_REQUIRE(scratch && scratch_bytes >= B * N * 8, RLS_EINVAL,
                     "N=%lld needs %lld B of scratch (rls_isco_maxcut_scratch_bytes), got %lld", (long long)N, (long long)(B * N * 8),
                     (long long)(scratch ? scratch_bytes : 0));
-        int Pg = 64;
-        while (Pg < 4096 && Pg < N && brow + (size_t)Pg * 16 + fixed <= (size_t)kLdsBytes) Pg <<= 1;
-        if (force_cap >= 2 && force_cap < Pg && (force_cap & (force_cap - 1)) == 0) Pg = force_cap;
-        const size_t lds_g = brow + (size_t)Pg * 8 + fixed;
-        IscoMcArgs ag{g->rowptr, g->col, use_ell ? g->ell_sym_ptr : nullptr, use_ell ? g->ell_sym : nullptr, x, y_out, B, N,
-                      path_length, temperature, u_gumbel, u_accept, seed, env_offset, energy_out, acc_out, terms_out, mask_out, Pg, lam,
-                      static_cast<float*>(scratch)};
-        ensure_dyn_lds((const void*)(k_isco_maxcut_step_wg<M, true>), lds_g);
-        hipLaunchKernelGGL((k_isco_maxcut_step_wg<M, true>), dim3((unsigned)B), dim3(kIscoWgWaves * kWave), lds_g, as_stream(stream), ag);
+    const bool use_ell = g->ell_sym_ptr && g->ell_sym && !g->wgt;
+    const IscoMcArgs a{g->rowptr, g->col, use_ell ? g->ell_sym_ptr : nullptr, use_ell ? g->ell_sym : nullptr, x, y_out, B, N,
+                       path_length, temperature, u_gumbel, u_accept, seed, env_offset, energy_out, acc_out, terms_out, mask_out,
+                       p.wg ? p.P : p.Pw, lam, p.grows ? static_cast<float*>(scratch) : nullptr};
+    const dim3 wg_block(kIscoWgWaves * kWave);
+    if (p.grows) {
+        ensure_dyn_lds((const void*)(k_isco_maxcut_step_wg<M, true>), p.lds);
+        hipLaunchKernelGGL((k_isco_maxcut_step_wg<M, true>), dim3((unsigned)B), wg_block, p.lds, as_stream(stream), a);
         return check_launch("k_isco_maxcut_step_wg<global rows>");
     }
-    const size_t rows = 2 * (((size_t)N + 7) & ~(size_t)7) + (size_t)N * 8;
-    int P = 1;
-    while (P < N) P <<= 1;
-    while (P > 64 && rows + (size_t)P * 8 + fixed > (size_t)kLdsBytes) P >>= 1;
-    if (force_cap >= 2 && force_cap < P && (force_cap & (force_cap - 1)) == 0) P = force_cap;
-    const size_t per_wave = rows + (size_t)P * 8;
-    RLS_REQUIRE(per_wave + fixed <= (size_t)kLdsBytes, RLS_EUNSUPPORTED, "N=%lld needs %zu B of LDS per env (max %d)", (long long)N,
-                per_wave + fixed, kLdsBytes);
-    const int force_wg = (int)knob(KN_ISCO_FORCE_WG, -1);      // dev knob: 0 wave per sample, 1 workgroup per sample
-    // The workgroup kernel (8-bit radix passes, node loops over 16 waves) also wins at LARGE batches from ~1500 nodes on: a wave's
-    // select is 32 one-bit passes over all its keys (from LDS past 2048 nodes) and its rows leave a CU ever fewer samples -- 4096
-    // samples (tools/timing/isco_kernels.py): N = 2000 485 vs 427 us, N = 4000 2121 vs 527, G70's 10^4 8410 vs 852, N = 15 000 14 526
-    // vs 1320; at N = 800 the wave kernel keeps the large batches (163 vs 301)
-    const bool use_wg = force_wg >= 0 ? (force_wg != 0 && N >= 4 * kWave)
-                                      : (B <= (int64_t)2 * num_cus() || N >= 1536) && N >= 4 * kWave && per_wave + fixed <= (size_t)kLdsBytes;
-    // wave-per-sample kernel: one wave per SIMD is latency-bound (round 3: 4 samples per CU), so the list gives up capacity for
-    // resident samples while it stays >= 512 entries -- the reference draws Poisson(~10) path lengths, a longer selection takes
-    // the extraction path -- G22-sized rows: 2048 entries x 4 samples -> 512 x 6 per CU, 4096 samples 606 -> 508 us
-    const int max_waves = (int)knob(KN_ISCO_WAVES, 8);     // dev knob (<= 8)
-    auto waves_for = [&](int cap) {
-        int wv = (int)((size_t)kLdsBytes / (rows + (size_t)cap * 8));
-        return wv > max_waves ? max_waves : wv;
-    };
-    int Pw = P;
-    if (!use_wg && force_cap == 0)
-        while (Pw > 512 && waves_for(Pw >> 1) > waves_for(Pw)) Pw >>= 1;
-    const int waves = waves_for(Pw) < 1 ? 1 : waves_for(Pw);
-    const size_t lds = (rows + (size_t)Pw * 8) * waves;
-    // few chains (the reference's configs run one): a workgroup per sample; from ~4 samples per CU on the wave-per-sample
-    // kernel has the throughput
-    const size_t lds_wg = per_wave + sizeof(IscoWgScratch) + 16;
-    if (use_wg) {
-        IscoMcArgs aw{g->rowptr, g->col, use_ell ? g->ell_sym_ptr : nullptr, use_ell ? g->ell_sym : nullptr, x, y_out, B, N,
-                      path_length, temperature, u_gumbel, u_accept, seed, env_offset, energy_out, acc_out, terms_out, mask_out, P, lam, nullptr};
-        if (lds_wg > 64 * 1024)
-            ensure_dyn_lds((const void*)(k_isco_maxcut_step_wg<M, false>), lds_wg);
-        hipLaunchKernelGGL((k_isco_maxcut_step_wg<M, false>), dim3((unsigned)B), dim3(kIscoWgWaves * kWave), lds_wg, as_stream(stream), aw);
+    if (p.wg) {
+        ensure_dyn_lds((const void*)(k_isco_maxcut_step_wg<M, false>), p.lds);
+        hipLaunchKernelGGL((k_isco_maxcut_step_wg<M, false>), dim3((unsigned)B), wg_block, p.lds, as_stream(stream), a);
         return check_launch("k_isco_maxcut_step_wg");
     }
-    IscoMcArgs a{g->rowptr, g->col, use_ell ? g->ell_sym_ptr : nullptr, use_ell ? g->ell_sym : nullptr, x, y_out, B, N, path_length, temperature, u_gumbel, u_accept, seed, env_offset,
-                 energy_out, acc_out, terms_out, mask_out, Pw, lam, nullptr};
-    if (lds > 64 * 1024)
-        ensure_dyn_lds((const void*)k_isco_maxcut_step<M>, lds);
-    hipLaunchKernelGGL(k_isco_maxcut_step<M>, dim3((unsigned)ceil_div(B, waves)), dim3(waves * kWave), lds, as_stream(stream), a);
+    ensure_dyn_lds((const void*)k_isco_maxcut_step<M>, p.lds);
+    hipLaunchKernelGGL(k_isco_maxcut_step<M>, dim3((unsigned)ceil_div(B, p.waves)), dim3(p.waves * kWave), p.lds, as_stream(stream), a);
     return check_launch("k_isco_maxcut_step");
 }
 
@@ -1289,9 +1041,10 @@ int rls_isco_mis_step(const rls_graph* g, const float* x, float* y_out, int64_t 
                                      acc_out, terms_out, mask_out, scratch, scratch_bytes, stream);
 }
 
-// The dense step: the product, then isco_step_launch's choices (list capacity, wave or workgroup per sample, the same knobs) with the
-// rows in LDS only -- the rows-in-scratch form is not built for it (A alone would be 0.5 GB at its sizes).  Every check comes
-// before the first launch, and the checks that read no pointer (sizes, temperature, the LDS limit) before the pointer checks.
+// The dense step: the product, then isco_plan_step's choices (list capacity -- at least 64 entries --, wave or workgroup per sample,
+// the same knobs) with the rows in LDS only -- the rows-in-scratch form is not built for it (A alone would be 0.5 GB at its sizes).
+// Every check comes before the first launch, and the checks that read no pointer (sizes, temperature, the LDS limit) before the
+// pointer checks.
 int rls_pisco_step(const uint16_t* adj, int64_t Np, const uint16_t* x, uint16_t* y_out, int64_t B, const int64_t* path_length,
                    float temperature, int32_t half_rounding, const float* u_gumbel, const float* u_accept, uint64_t seed,
                    int64_t env_offset, float* energy_out, float* acc_out, float* terms_out, uint8_t* mask_out, void* scratch,
@@ -1300,12 +1053,10 @@ int rls_pisco_step(const uint16_t* adj, int64_t Np, const uint16_t* x, uint16_t*
     RLS_REQUIRE(B >= 0, RLS_EINVAL, "B < 0");
     if (B == 0) return RLS_OK;
     RLS_REQUIRE(temperature > 0.0f, RLS_EINVAL, "temperature must be > 0");
-    const int64_t N = Np;
-    const size_t fixed = sizeof(IscoWgScratch) + 16;
-    const size_t rows = 2 * (size_t)N + (size_t)N * 8;
-    RLS_REQUIRE(rows + 64 * 8 + fixed <= (size_t)kLdsBytes, RLS_EUNSUPPORTED,
+    const IscoPlan p = isco_plan_step(isco_rows_bytes(Np), Np, B, num_cus(), kIscoMinList, false);
+    RLS_REQUIRE(p.err == RLS_OK, p.err,
                 "Np=%lld: a sample's rows and the smallest list need %zu B of LDS (max %d); the dense step has no rows-in-scratch form",
-                (long long)N, rows + 64 * 8 + fixed, kLdsBytes);
+                (long long)Np, p.need, kLdsBytes);
     RLS_REQUIRE(adj && x && y_out && path_length, RLS_EINVAL, "NULL pointer");
     RLS_REQUIRE((u_gumbel == nullptr) == (u_accept == nullptr), RLS_EINVAL, "u_gumbel and u_accept must both be given or both be NULL");
     RLS_REQUIRE((const void*)x != (const void*)y_out, RLS_EINVAL, "y_out must not alias x (a rejected proposal restores x)");
@@ -1316,36 +1067,15 @@ int rls_pisco_step(const uint16_t* adj, int64_t Np, const uint16_t* x, uint16_t*
     float* r = static_cast<float*>(scratch);
     int32_t* ord = reinterpret_cast<int32_t*>(r + B * Np);
     if (int rc = rls_pisco_product(adj, Np, x, B, r, stream)) return rc;
-    const int force_cap = (int)knob(KN_ISCO_SEL_CAP, 0);
-    int P = 1;
-    while (P < N) P <<= 1;
-    if (P < 64) P = 64;
-    while (P > 64 && rows + (size_t)P * 8 + fixed > (size_t)kLdsBytes) P >>= 1;
-    if (force_cap >= 2 && force_cap < P && (force_cap & (force_cap - 1)) == 0) P = force_cap;
-    const size_t per_wave = rows + (size_t)P * 8;
-    const int force_wg = (int)knob(KN_ISCO_FORCE_WG, -1);
-    const bool use_wg = force_wg >= 0 ? (force_wg != 0 && N >= 4 * kWave) : (B <= (int64_t)2 * num_cus() || N >= 1536) && N >= 4 * kWave;
-    PiscoArgs a{adj, N, x, y_out, B, path_length, temperature, half_rounding, u_gumbel, u_accept, seed, env_offset,
-                energy_out, acc_out, terms_out, mask_out, P, r, ord};
-    if (use_wg) {
-        const size_t lds_wg = per_wave + fixed;
-        ensure_dyn_lds((const void*)k_pisco_step_wg, lds_wg);
-        hipLaunchKernelGGL(k_pisco_step_wg, dim3((unsigned)B), dim3(kIscoWgWaves * kWave), lds_wg, as_stream(stream), a);
+    const PiscoArgs a{adj, Np, x, y_out, B, path_length, temperature, half_rounding, u_gumbel, u_accept, seed, env_offset,
+                      energy_out, acc_out, terms_out, mask_out, p.wg ? p.P : p.Pw, r, ord};
+    if (p.wg) {
+        ensure_dyn_lds((const void*)k_pisco_step_wg, p.lds);
+        hipLaunchKernelGGL(k_pisco_step_wg, dim3((unsigned)B), dim3(kIscoWgWaves * kWave), p.lds, as_stream(stream), a);
         return check_launch("k_pisco_step_wg");
     }
-    const int max_waves = (int)knob(KN_ISCO_WAVES, 8);
-    auto waves_for = [&](int cap) {
-        int wv = (int)((size_t)kLdsBytes / (rows + (size_t)cap * 8));
-        return wv > max_waves ? max_waves : wv;
-    };
-    int Pw = P;
-    if (force_cap == 0)
-        while (Pw > 512 && waves_for(Pw >> 1) > waves_for(Pw)) Pw >>= 1;
-    const int waves = waves_for(Pw) < 1 ? 1 : waves_for(Pw);
-    a.P = Pw;
-    const size_t lds = (rows + (size_t)Pw * 8) * waves;
-    ensure_dyn_lds((const void*)k_pisco_step, lds);
-    hipLaunchKernelGGL(k_pisco_step, dim3((unsigned)ceil_div(B, waves)), dim3(waves * kWave), lds, as_stream(stream), a);
+    ensure_dyn_lds((const void*)k_pisco_step, p.lds);
+    hipLaunchKernelGGL(k_pisco_step, dim3((unsigned)ceil_div(B, p.waves)), dim3(p.waves * kWave), p.lds, as_stream(stream), a);
     return check_launch("k_pisco_step");
 }
 

@@ -4,7 +4,7 @@
 // EXACTLY-sized heap buffers, built with -fsanitize=address,undefined by tests/test_sanitize.py.  Every builder runs
 // its sizing call first and then fills buffers of exactly that size, so a one-past-the-end write is an ASAN report;
 // structural invariants (every node scheduled once, levels respect the dependency order, ELL rows complete) are checked
-// on top.  The MaxCut launch planner (csrc/rls_maxcut_plan.h, host-only C++) runs over random shapes beside them.  Exit code 0 = clean.  CPU only: sanitizers do not run on the GPU box.
+// on top.  The launch planners (csrc/rls_maxcut_plan.h, rls_tsp_plan.h, rls_isco_plan.h: host-only C++) run over random shapes beside them.  Exit code 0 = clean.  CPU only: sanitizers do not run on the GPU box.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -16,6 +16,7 @@
 #include "rlsolver_hip.h"
 #include "rls_maxcut_plan.h"      // the MaxCut launch planner: host-only C++, so it runs under the sanitizers too
 #include "rls_tsp_plan.h"         // ... and the TSP one
+#include "rls_isco_plan.h"        // ... and the ISCO steps'
 
 #include "../oracle/oracle.h"
 
@@ -277,6 +278,38 @@ static void run_planners(std::mt19937_64& rng) {
               "TSP form N %lld K %d err %d lds %zu block %d waves %d", (long long)tn, tk, p.err, p.lds, p.block, p.waves);
 }
 
+// the ISCO steps' planner (graph and dense) over random (N, B) up to past every LDS limit, under every combination of its four dev
+// knobs: a plan fits LDS, its lists are powers of two of at least 64 entries (or hold every node of a smaller graph, or are the
+// forced capacity), 1..8 samples share a workgroup, and only rows of >= 256 nodes in LDS get a workgroup per sample by choice
+static void run_isco_plans(std::mt19937_64& rng) {
+    const int64_t caps[] = {-1, 16, 64, 1024}, wgs[] = {-1, 0, 1}, grs[] = {-1, 1}, wvs[] = {-1, 1, 4, 8};
+    auto set = [](const char* name, int64_t v) { if (v >= 0) rls_tuning_set(name, v); };
+    auto pow2 = [](int v) { return v >= 1 && (v & (v - 1)) == 0; };
+    for (int k = 0; k < 8; ++k) {
+        const int64_t N = k == 0 ? 8 * (1 + (int64_t)(rng() % 40)) : 1 + (int64_t)(rng() % (k < 4 ? 20000 : 100000));
+        const int64_t B = 1 + (int64_t)(rng() % (1 << 15));
+        const int cus = 1 + (int)(rng() % 512);
+        for (int64_t cap : caps) for (int64_t wg : wgs) for (int64_t gr : grs) for (int64_t wv : wvs) {
+            set("RLS_ISCO_SEL_CAP", cap); set("RLS_ISCO_FORCE_WG", wg); set("RLS_ISCO_GLOBAL_ROWS", gr); set("RLS_ISCO_WAVES", wv);
+            for (int dense = 0; dense < 2; ++dense) {
+                const int64_t n = dense ? (N + 7) / 8 * 8 : N;
+                const rls::IscoPlan p = rls::isco_plan_step(rls::isco_rows_bytes(n), n, B, cus, dense ? rls::kIscoMinList : 1, !dense);
+                if (p.err != RLS_OK) {
+                    CHECK(p.err == RLS_EUNSUPPORTED && p.need > (size_t)rls::kLdsBytes, "ISCO plan N %lld refused at %zu B", (long long)n, p.need);
+                    continue;
+                }
+                auto list_ok = [&](int P) { return pow2(P) && (P >= rls::kIscoMinList || P == cap || (!dense && P >= n)); };
+                CHECK(p.lds <= (size_t)rls::kLdsBytes && list_ok(p.P) && list_ok(p.Pw) && p.Pw <= p.P && p.waves >= 1 && p.waves <= 8 &&
+                          (!p.grows || (p.wg && !dense)) && (!p.wg || p.grows || n >= 256),
+                      "ISCO plan N %lld B %lld dense %d knobs %lld %lld %lld %lld: P %d Pw %d waves %d wg %d grows %d lds %zu", (long long)n,
+                      (long long)B, dense, (long long)cap, (long long)wg, (long long)gr, (long long)wv, p.P, p.Pw, p.waves, (int)p.wg,
+                      (int)p.grows, p.lds);
+            }
+            rls_tuning_unset(nullptr);
+        }
+    }
+}
+
 // the MaxSAT level schedule (rls_maxsat_visit_levels) over random formulas: k-SAT with repeated variables, long clauses, empty
 // clauses, a hub variable, weighted or not, a random visiting order -- sized, then filled into buffers of exactly that size; every
 // entry points inside the tile, every variable sits in exactly one lane, a buffer one word short is refused
@@ -339,6 +372,7 @@ int main(int argc, char** argv) {
         run_builders(g, rng);
         run_oracle(g, rng);
         for (int k = 0; k < 50; ++k) run_planners(rng);
+        run_isco_plans(rng);
         run_maxsat(rng, it);
     }
     std::printf("host_sanitize: %d random graphs through the host builders and the C oracle, clean\n", iters);
