@@ -14,7 +14,9 @@
 //   MODE 3  MODE 2's staging with the stores chasing the loads, the flip applied in registers
 // MODE 2 on 1-byte rows with write-through stores (the headline's form) requests obj, the CSR
 // row bounds and the neighbour ids beside the run, so that the LDS stage is held for one memory
-// latency, not for a chain of them; the other staged forms keep the order of round 7.
+// latency, not for a chain of them; the other staged forms keep the order of round 7.  Since round 9 it
+// reads all bytes of the gain from LDS before one wait and flips with one LDS write; a call with full runs,
+// no cur / done and no CSR row longer than a wave runs that trip as a kernel of its own, k_maxcut_step_lean.
 #include "rls_tile.h"
 #include <cstdlib>
 
@@ -353,41 +355,44 @@ __global__ __launch_bounds__(256) void k_maxcut_step(const T* __restrict__ xin, 
                     if constexpr (WEIGHTED) asm volatile("" : "+v"(wv[k]) :: "memory");
                 }
             };
-            // gains from the staged (unpatched) rows
+            // gains from the staged (unpatched) rows.  All 2 x EPW reads are issued before ONE wait (round 9; before, two LDS round
+            // trips per env, one after the other, with the stage held idle): nothing is read under a branch, and every index is in
+            // bounds whatever the action -- an invalid one reads byte 0 of its row (a row past a short run's end: unwritten LDS of this
+            // wave's region), a lane past the CSR row's end holds the row's first neighbour, a node without neighbours holds 0.
+            T ba[EPW], bn[EPW];
             auto gather = [&]() {
 #pragma unroll
-                for (int k = 0; k < EPW; ++k)
-                    if (act[k] >= 0) {
-                        const T* row = stage + (int64_t)k * N;
-                        const bool xa = spin_is_set(row[act[k]]);
-                        int d;
-                        if (deg[k] <= kWave) {
-                            const bool on = lane < deg[k];
-                            const bool xn = on ? spin_is_set(row[nb[k]]) : xa;
-                            if constexpr (WEIGHTED) d = wave_sum_i32(on ? ((xn == xa) ? wv[k] : -wv[k]) : 0);
-                            else d = deg[k] - 2 * __popcll(ballot64(xn != xa));
-                        } else {
-                            d = flip_gain<T, WEIGHTED>(row, act[k], rowptr, col, wgt, lane);
-                        }
-                        if (lane == k) my_delta = d;
-                    }
+                for (int k = 0; k < EPW; ++k) {
+                    const T* row = stage + (int64_t)k * N;
+                    ba[k] = row[act[k] < 0 ? 0 : act[k]];
+                    bn[k] = row[nb[k]];
+                }
+#pragma unroll
+                for (int k = 0; k < EPW; ++k) {
+                    const bool xa = spin_is_set(ba[k]), xn = spin_is_set(bn[k]);
+                    const bool on = lane < deg[k];
+                    int d;   // (of an invalid action: node 0's, unused)
+                    if constexpr (WEIGHTED) d = wave_sum_i32(on ? ((xn == xa) ? wv[k] : -wv[k]) : 0);
+                    else d = deg[k] - 2 * __popcll(ballot64(on && xn != xa));
+                    if (act[k] >= 0 && deg[k] > kWave) d = flip_gain<T, WEIGHTED>(stage + (int64_t)k * N, act[k], rowptr, col, wgt, lane);
+                    if (lane == k && act[k] >= 0) my_delta = d;
+                }
             };
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_wave_barrier();
             operands_landed();
             gather();
             publish_from(obj_old);
-            __builtin_amdgcn_wave_barrier();
+            // the flip: ONE LDS write of the byte the gather has read already (lane k holds env k's), not a read-modify-write with a
+            // wait and a barrier of its own.  A wave's LDS instructions execute in order, so the store loop's reads, issued after
+            // it, see the flipped byte (tools/ceilings/ring_step_ladder.hip, rung i against rung e: -0.51 us)
             if (lane < nenv) {
                 int64_t a = -1;
+                T old = 0;
 #pragma unroll
-                for (int k = 0; k < EPW; ++k) if (lane == k) a = act[k];
-                if (a >= 0) {
-                    T* p = stage + (int64_t)lane * N + a;
-                    *p = spin_flip<T>(*p);
-                }
+                for (int k = 0; k < EPW; ++k) if (lane == k) { a = act[k]; old = ba[k]; }
+                if (a >= 0) stage[(int64_t)lane * N + a] = spin_flip<T>(old);
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_wave_barrier();
 #pragma unroll 4
             for (int64_t slot0 = 0; slot0 < nvec + h_out; slot0 += kWave) {
@@ -552,6 +557,97 @@ __global__ __launch_bounds__(256) void k_maxcut_step(const T* __restrict__ xin, 
   }   // runs of this wave
 }
 
+// The headline's own kernel (round 9): the trip of k_maxcut_step's MODE 2 / 1-byte rows / write-through form, one-shot grid, for a
+// call in which every run is full (B % EPW == 0), cur == done == NULL and no CSR row is longer than a wave (max_degree <= 64, an
+// upper bound by the ABI) -- what bench.py's rollout loop and a PPO rollout without cur / done ask for.  Nothing is compiled in
+// for what such a call cannot need: the loop over runs, the short run and its element tail, the gather's loop for long rows, the
+// cur / done stores; indices inside a run are 32-bit (a staged run fits the LDS).  It is tools/ceilings/ring_step_ladder.hip's rung i
+// with K4's arguments.  Any other call runs k_maxcut_step.  The INVARIANT of the hand-issued loads (see there) holds here too.
+template <int EPW>
+__global__ __launch_bounds__(256) void k_maxcut_step_lean(const uint8_t* __restrict__ xin, uint8_t* __restrict__ xout, int64_t B, int N,
+                                                          const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                                          const int64_t* __restrict__ action, int32_t* __restrict__ obj,
+                                                          float* __restrict__ reward, int align_lines) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
+    const int64_t b0 = ((int64_t)blockIdx.x * (blockDim.x / kWave) + wib) * EPW;
+    if (b0 >= B) return;                                    // (a last workgroup with fewer runs than waves)
+    const int run = EPW * N, nvec = run >> 4;               // bytes and 16-byte vectors of a run
+    const u32x4* src = reinterpret_cast<const u32x4*>(xin + b0 * N);
+    u32x4* dst = reinterpret_cast<u32x4*>(xout + b0 * N);
+    const int h_in = align_lines ? (int)((reinterpret_cast<uintptr_t>(src) >> 4) & 7) : 0;
+    const int h_out = align_lines ? (int)((reinterpret_cast<uintptr_t>(dst) >> 4) & 7) : 0;
+    u32x4* region_v = reinterpret_cast<u32x4*>(smem + (size_t)wib * ((size_t)run + kStepPad));
+    u32x4* stage_v = region_v + h_in;
+    uint8_t* stage = reinterpret_cast<uint8_t*>(stage_v);
+
+    int act[EPW];
+#pragma unroll
+    for (int k = 0; k < EPW; ++k) {
+        const int64_t a = action[b0 + k];
+        act[k] = ((uint64_t)a < (uint64_t)N) ? (int)a : -1;
+    }
+    int obj_old;
+    {
+        const int32_t* po = obj + b0 + (lane < EPW ? lane : 0);
+        asm volatile("global_load_dword %0, %1, off" : "=v"(obj_old) : "v"(po) : "memory");
+    }
+    for (int s0 = 0; s0 < nvec + h_in; s0 += kWave) {
+        const int i = s0 + lane - h_in;
+        if (i >= 0 && i < nvec) glds16<true>(src + i, region_v + s0);
+    }
+    int r0[EPW], deg[EPW], nb[EPW];
+#pragma unroll
+    for (int k = 0; k < EPW; ++k) {
+        const int ai = act[k] < 0 ? 0 : act[k];
+        r0[k] = rowptr[ai];
+        deg[k] = rowptr[ai + 1];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int k = 0; k < EPW; ++k) {
+        nb[k] = 0;
+        deg[k] -= r0[k];
+        if (act[k] >= 0 && deg[k] > 0) {
+            const int32_t* pn = col + r0[k] + (lane < deg[k] ? lane : 0);
+            asm volatile("global_load_dword %0, %1, off" : "=v"(nb[k]) : "v"(pn) : "memory");
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");     // the run has landed, and every operand with it
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("" : "+v"(obj_old) :: "memory");
+#pragma unroll
+    for (int k = 0; k < EPW; ++k) asm volatile("" : "+v"(nb[k]) :: "memory");
+    uint8_t ba[EPW], bn[EPW];                                       // all 2 x EPW reads of the gather, one wait (indices: see k_maxcut_step)
+#pragma unroll
+    for (int k = 0; k < EPW; ++k) {
+        const uint8_t* row = stage + k * N;
+        ba[k] = row[act[k] < 0 ? 0 : act[k]];
+        bn[k] = row[nb[k]];
+    }
+    int my_delta = 0, a = -1;
+    uint8_t old = 0;
+#pragma unroll
+    for (int k = 0; k < EPW; ++k) {
+        const bool xa = spin_is_set(ba[k]), xn = spin_is_set(bn[k]);
+        const int d = deg[k] - 2 * __popcll(ballot64(lane < deg[k] && xn != xa));
+        if (lane == k) { a = act[k]; old = ba[k]; }
+        if (lane == k && act[k] >= 0) my_delta = d;
+    }
+    if (lane < EPW) {
+        obj[b0 + lane] = obj_old + my_delta;
+        reward[b0 + lane] = a >= 0 ? (float)my_delta : __builtin_nanf("");
+        if (a >= 0) stage[lane * N + a] = spin_flip<uint8_t>(old);  // one LDS write; the store loop's reads follow it in order
+    }
+    __builtin_amdgcn_wave_barrier();
+    // (reading several pieces from LDS before the first is stored was measured and does not pay: the ladder's rung k)
+    for (int s0 = 0; s0 < nvec + h_out; s0 += kWave) {
+        const int i = s0 + lane - h_out;
+        if (i >= 0 && i < nvec) st_vec<kStWt>(dst + i, stage_v[i]);
+    }
+}
+
 // tuning knobs (rls_tuning_set; no environment variable is read by the production library): nts = -1 automatic | 0 | 1
 // (nontemporal stores), epw / wpb = 0: automatic, persist = -1 automatic | 0 one run per wave | k: k workgroup rounds per CU
 // resident, waves loop; chase = -1 automatic | 0 MODE 2 (stores after the last load) | 1 MODE 3 (stores chase the loads);
@@ -594,6 +690,8 @@ extern "C" int rls_maxcut_step(const rls_graph* g, const void* x_in, void* x_out
                 RLS_EINVAL, "x_in and x_out overlap partially");
     const StepKnobs knobs = step_knobs();
     // envs per wave: the largest of {8,4,2,1} whose staged run fits ~8 KB of LDS per wave (G22: 4) ...
+    // (re-measured in round 9 on the lean kernel, profiles/r09_sweep.txt, G22 shape: EPW 4 x 4 waves 39.0 us, 8 x 4 39.0, 8 x 1 39.1,
+    // 4 x 2 39.7, every other point 41.8 - 48.0: the rule stands)
     int epw_auto = 8;
     while (epw_auto > 1 && (int64_t)epw_auto * N * spin_bytes > 8192) epw_auto >>= 1;
     // ... but at least enough rows for a run to be a whole number of 16-byte vectors (N = 1000 bytes: >= 2 rows,
@@ -667,6 +765,20 @@ extern "C" int rls_maxcut_step(const rls_graph* g, const void* x_in, void* x_out
         else LAUNCH_STEP(T, 2, true, true, true, kStPlain);                                 \
     } while (0)
     RLS_REQUIRE(emit || epw == 4, RLS_EINVAL, "the in-place step runs 4 envs per wave");
+    // k_maxcut_step_lean where the call is what it is written for (see there): the write-through MODE 2 form on 1-byte rows with a
+    // one-shot grid, every run full, no cur / done, no row longer than a wave.  Round 9, interleaved A/B at the G22 shape
+    // (profiles/r09_bench_ab.txt): plain bench.py 40.13 / 40.15 -> 39.12 / 39.10 us, --steps 20 40.48 .. 40.75 -> 39.57 .. 39.61; the
+    // new gather and flip inside k_maxcut_step alone gave 0.4 of that 1.0 us (DESIGN_HISTORY.md section 13)
+    const bool lean = staged && wt && !chase && spin_bytes == 1 && (epw == 1 || epw == 2 || epw == 4 || epw == 8) && B % epw == 0 &&
+                      !cur && !done && g->max_degree <= kWave && nblocks == ceil_div(ceil_div(B, epw), waves_per_block);
+    if (lean) {
+        void (*kern)(const uint8_t*, uint8_t*, int64_t, int, const int32_t*, const int32_t*, const int64_t*, int32_t*, float*, int) =
+            epw == 1 ? k_maxcut_step_lean<1> : epw == 2 ? k_maxcut_step_lean<2> : epw == 8 ? k_maxcut_step_lean<8> : k_maxcut_step_lean<4>;
+        if (lds > 64 * 1024) ensure_dyn_lds((const void*)kern, lds);
+        hipLaunchKernelGGL(kern, grid, block, lds, s, (const uint8_t*)x_in, (uint8_t*)x_out, B, (int)N, g->rowptr, g->col, action, obj,
+                           reward, knobs.align);
+        return check_launch("k_maxcut_step_lean");
+    }
     if (spin_bytes == 1) DISPATCH_T(uint8_t);
     else DISPATCH_T(float);
 #undef DISPATCH_T

@@ -8,9 +8,19 @@
 //        other, then the flipped byte patched in LDS: K4's order before round 8
 //   e  the work of d in K4's order since round 8: obj requested before the run, all rowptr pairs in one batch and all col loads
 //        beside the run, ONE wait, gather, obj written from the preloaded value
+//   f  e with the per-env outputs leaving once per workgroup: every wave deposits obj_old + delta and reward in an LDS mailbox, the
+//        wave that arrives last (LDS fetch-add, no wave waits for another) stores the workgroup's 64 bytes of each array
+//   g  f with a shorter trip after landing: all 2 x EPW gather reads issued before one wait, the flip applied in registers in the
+//        store loop (no LDS read-modify-write, no wait and wave barrier of its own)
+//   h  g with the publisher's two stores write-through (sc1) as well: the launch leaves no dirty line in the L2s
+//   i  e (per-wave outputs, no mailbox) with one wait for all 2 x EPW gather reads and the flip as ONE LDS write of the byte the
+//        gather has read, no read-modify-write, no wait, no barrier: measured against e
+//   j  i with the wave's obj / reward stores write-through (sc1)
+//   k  i with the store loop reading 8 pieces of the run from LDS before it stores the first: measured against i
+// (rungs f - k are a kernel of their own, k_rung_wg; `vs below` of i is against e: the rungs a - e stay the code round 8 measured)
 // The graph is synthetic: N nodes of degree 20, node i's row = i + 1 + 97 j mod N, j = 0..19 (N is refused where two of these
 // coincide or one is i itself).  16 random action vectors, pass k takes vector k % 16.  All rungs interleaved in one process, 5 rounds
-// of 200 passes.  Before it is timed, every rung's pass 0 is checked against the host: the output slot is the input (rungs d, e: with
+// of 200 passes; the spread of a rung is the max - min of its five rounds.  Before it is timed, every rung's pass 0 is checked against the host: the output slot is the input (rungs d, e: with
 // each env's action byte flipped), reward and obj's change are what the rung is meant to compute -- a rung that dropped work fails.
 // Build: hipcc --offload-arch=gfx950 -O3 -o /tmp/ring_step_ladder tools/ceilings/ring_step_ladder.hip
 // Run:   /tmp/ring_step_ladder [B N]     (default: the G22 shape 65536 2000; B a multiple of 4, 4 N a multiple of 16)
@@ -144,6 +154,238 @@ __global__ __launch_bounds__(256) void k_rung(const unsigned char* __restrict__ 
     }
 }
 
+__device__ __forceinline__ u32x4 flip_byte(u32x4 v, int word, int sh) {   // logical_not of the byte at bit `sh` of dword `word`
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const uint32_t d = v[q];
+        const uint32_t nb = (((d >> sh) & 0xffu) == 0) ? 1u : 0u;
+        const uint32_t nd = (d & ~(0xffu << sh)) | (nb << sh);
+        v[q] = (q == word) ? nd : d;
+    }
+    return v;
+}
+
+// bytes of the workgroup's mailbox behind its kWpb stages: obj and reward of kWpb * kEpw envs, the arrival counter
+constexpr int kMailbox = kWpb * kEpw * 8 + 16;
+constexpr int kStoreBatch = 8;   // rung k: 1 KB pieces read from LDS before the first is stored
+
+template <int RUNG>   // 5 .. 10 = f .. k
+__global__ __launch_bounds__(256) void k_rung_wg(const unsigned char* __restrict__ xin, unsigned char* __restrict__ xout, int64_t B, int64_t N,
+                                                 const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                                 const int64_t* __restrict__ action, int32_t* __restrict__ obj, float* __restrict__ reward) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
+    int* mb_obj = reinterpret_cast<int*>(smem + (size_t)kWpb * ((size_t)kEpw * N + kPad));
+    float* mb_rew = reinterpret_cast<float*>(mb_obj + kWpb * kEpw);
+    unsigned* mb_arrived = reinterpret_cast<unsigned*>(mb_rew + kWpb * kEpw);
+    constexpr bool MAILBOX = RUNG <= 7;                 // f, g, h: outputs once per workgroup; i, j: per wave, as in e
+    constexpr bool REGFLIP = RUNG == 6 || RUNG == 7;    // g, h: flip in registers in the store loop
+    constexpr bool BLINDFLIP = RUNG >= 8;               // i, j: flip written to LDS from the byte the gather has read
+    constexpr bool SC1 = RUNG == 7 || RUNG == 9;        // h, j: obj / reward stored write-through
+    if constexpr (MAILBOX) {
+        if (threadIdx.x == 0) *mb_arrived = 0;
+        __syncthreads();                  // before any load is issued; a wave without a run leaves only behind it
+    }
+    const int64_t wg_b0 = (int64_t)blockIdx.x * kWpb * kEpw;
+    const int64_t b0 = wg_b0 + (int64_t)wib * kEpw;
+    if (b0 >= B) return;
+    const int64_t wg_runs = (B - wg_b0 + kEpw - 1) / kEpw;
+    const unsigned expected = (unsigned)(wg_runs < kWpb ? wg_runs : kWpb);      // the waves of this workgroup that have a run
+    const int nenv = (int)((B - b0) < kEpw ? (B - b0) : kEpw);
+    const int64_t nvec = (int64_t)nenv * N / 16;
+    const u32x4* src = reinterpret_cast<const u32x4*>(xin + b0 * N);
+    u32x4* dst = reinterpret_cast<u32x4*>(xout + b0 * N);
+    const int h_in = (int)((reinterpret_cast<uintptr_t>(src) >> 4) & 7), h_out = (int)((reinterpret_cast<uintptr_t>(dst) >> 4) & 7);
+    u32x4* region = reinterpret_cast<u32x4*>(smem + (size_t)wib * ((size_t)kEpw * N + kPad));
+    u32x4* stage_v = region + h_in;
+    unsigned char* stage = reinterpret_cast<unsigned char*>(stage_v);
+
+    int64_t act[kEpw];
+#pragma unroll
+    for (int k = 0; k < kEpw; ++k) {
+        const int64_t a = (k < nenv) ? action[b0 + k] : -1;
+        act[k] = ((uint64_t)a < (uint64_t)N) ? a : -1;
+    }
+    // where the flips fall in the run (rungs g, h), worked out while the run is in flight: piece of the store loop, lane, dword, bit (a run is < 2^31 bytes)
+    int fj[kEpw], fl[kEpw], fq[kEpw], fsh[kEpw];
+#pragma unroll
+    for (int k = 0; k < kEpw; ++k) {
+        const int rel = act[k] < 0 ? 0 : k * (int)N + (int)act[k];
+        const int slot = (rel >> 4) + (int)((reinterpret_cast<uintptr_t>(xout + b0 * N) >> 4) & 7);      // + h_out
+        fj[k] = act[k] < 0 ? -1 : slot >> 6; fl[k] = slot & 63; fq[k] = (rel >> 2) & 3; fsh[k] = (rel & 3) * 8;
+    }
+    int obj_old;
+    {
+        const int32_t* po = obj + b0 + (lane < nenv ? lane : 0);
+        asm volatile("global_load_dword %0, %1, off" : "=v"(obj_old) : "v"(po) : "memory");
+    }
+    for (int64_t s0 = 0; s0 < nvec + h_in; s0 += kWave) {
+        const int64_t i = s0 + lane - h_in;
+        if (i >= 0 && i < nvec)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + i),
+                                             (__attribute__((address_space(3))) void*)(region + s0), 16, 0, 2);
+    }
+    int r0[kEpw], deg[kEpw], nb[kEpw];
+#pragma unroll
+    for (int k = 0; k < kEpw; ++k) {
+        const int64_t ai = act[k] < 0 ? 0 : act[k];
+        r0[k] = rowptr[ai];
+        deg[k] = rowptr[ai + 1];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int k = 0; k < kEpw; ++k) {
+        nb[k] = 0;
+        deg[k] -= r0[k];
+        if (act[k] >= 0 && deg[k] > 0) {
+            const int32_t* pn = col + r0[k] + (lane < deg[k] ? lane : 0);
+            asm volatile("global_load_dword %0, %1, off" : "=v"(nb[k]) : "v"(pn) : "memory");
+        }
+    }
+    if constexpr (REGFLIP) {
+#pragma unroll
+        for (int k = 0; k < kEpw; ++k) asm volatile("" : "+s"(fj[k]), "+s"(fl[k]), "+s"(fq[k]), "+s"(fsh[k]));    // (computed HERE, not sunk behind the wait)
+    }
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");     // the run has landed, and every operand with it
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("" : "+v"(obj_old) :: "memory");
+#pragma unroll
+    for (int k = 0; k < kEpw; ++k) asm volatile("" : "+v"(nb[k]) :: "memory");
+    int my_delta = 0;
+    unsigned char ba[kEpw], bn[kEpw];
+    if constexpr (RUNG == 5) {
+#pragma unroll
+        for (int k = 0; k < kEpw; ++k)
+            if (act[k] >= 0) {
+                const unsigned char* row = stage + (int64_t)k * N;
+                const bool xa = row[act[k]] != 0;
+                const bool on = lane < deg[k];
+                const bool xn = on ? row[nb[k]] != 0 : xa;
+                const int d = deg[k] - 2 * __popcll(__builtin_amdgcn_ballot_w64(xn != xa));
+                if (lane == k) my_delta = d;
+            }
+    } else {
+        // every read of the gather before one wait: the indices are in bounds whatever the action (an invalid one reads byte 0 of
+        // its row; a lane past the row's end holds the row's first neighbour, a node without neighbours 0)
+#pragma unroll
+        for (int k = 0; k < kEpw; ++k) {
+            const unsigned char* row = stage + (int64_t)k * N;
+            ba[k] = row[act[k] < 0 ? 0 : act[k]];
+            bn[k] = row[nb[k]];
+        }
+#pragma unroll
+        for (int k = 0; k < kEpw; ++k) {
+            const bool xa = ba[k] != 0, xn = bn[k] != 0;
+            const int d = deg[k] - 2 * __popcll(__builtin_amdgcn_ballot_w64(lane < deg[k] && xn != xa));
+            if (lane == k && act[k] >= 0) my_delta = d;
+        }
+    }
+    int64_t a = -1;
+#pragma unroll
+    for (int k = 0; k < kEpw; ++k) if (lane == k) a = act[k];
+    if constexpr (!MAILBOX) {
+        // i, j: the wave publishes its own entries as in e; the flip is ONE LDS write of the byte the gather has read already (lane k
+        // holds env k's), with no read, no wait and no barrier of its own -- a wave's LDS instructions execute in order, so the store
+        // loop's reads, issued later, see it
+        if (lane < nenv) {
+            const int v = obj_old + my_delta;
+            const float r = a >= 0 ? (float)my_delta : __builtin_nanf("");
+            if constexpr (SC1) {
+                asm volatile("global_store_dword %0, %1, off sc1" :: "v"(obj + b0 + lane), "v"(v) : "memory");
+                asm volatile("global_store_dword %0, %1, off sc1" :: "v"(reward + b0 + lane), "v"(r) : "memory");
+            } else {
+                obj[b0 + lane] = v;
+                reward[b0 + lane] = r;
+            }
+            unsigned char old = 0;
+#pragma unroll
+            for (int k = 0; k < kEpw; ++k) if (lane == k) old = ba[k];
+            if (a >= 0) stage[(int64_t)lane * N + a] = old == 0 ? 1 : 0;
+        }
+        __builtin_amdgcn_wave_barrier();
+        if constexpr (RUNG >= 10) {
+            // k: the store loop reads kStoreBatch pieces from LDS before it stores the first (an LDS read of a clamped index needs no
+            // branch): the reads' latencies overlap instead of one round trip per 1 KB piece
+            const int nv = (int)nvec;
+            for (int s0 = 0; s0 < nv + h_out; s0 += kStoreBatch * kWave) {
+                u32x4 v[kStoreBatch];
+#pragma unroll
+                for (int q = 0; q < kStoreBatch; ++q) {
+                    const int i = s0 + q * kWave + lane - h_out;
+                    v[q] = stage_v[i < 0 ? 0 : (i < nv ? i : nv - 1)];
+                }
+#pragma unroll
+                for (int q = 0; q < kStoreBatch; ++q) {
+                    const int i = s0 + q * kWave + lane - h_out;
+                    if (i >= 0 && i < nv) store16_wt(dst + i, v[q]);
+                }
+            }
+            return;
+        }
+        for (int64_t s0 = 0; s0 < nvec + h_out; s0 += kWave) {
+            const int64_t i = s0 + lane - h_out;
+            if (i >= 0 && i < nvec) store16_wt(dst + i, stage_v[i]);
+        }
+        return;
+    }
+    if (lane < nenv) {
+        mb_obj[wib * kEpw + lane] = obj_old + my_delta;
+        mb_rew[wib * kEpw + lane] = a >= 0 ? (float)my_delta : __builtin_nanf("");
+        if constexpr (RUNG == 5) {
+            if (a >= 0) {
+                unsigned char* p = stage + (int64_t)lane * N + a;
+                *p = *p == 0 ? 1 : 0;
+            }
+        }
+    }
+    // arrive: this wave's deposits are released (nothing is outstanding on the vector counter here, so the fence costs the LDS wait
+    // that rung e has at this point anyway); the fetch-add's answer is not looked at before the run's stores have been issued
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    unsigned before = 0;
+    if (lane == 0) before = __hip_atomic_fetch_add(mb_arrived, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if constexpr (RUNG == 5) __builtin_amdgcn_wave_barrier();
+    if constexpr (RUNG == 5) {
+        for (int64_t s0 = 0; s0 < nvec + h_out; s0 += kWave) {
+            const int64_t i = s0 + lane - h_out;
+            if (i >= 0 && i < nvec) store16_wt(dst + i, stage_v[i]);
+        }
+    } else {
+        // (piece j of the store loop holds vector fv at lane fl of piece fj: a scalar compare per env and piece, the lane compare and
+        // the flip only in the one piece that holds it -- a per-lane `i == fv[k]` costs the loop a vector compare and a branch per env)
+        const int nv = (int)nvec;
+        for (int j = 0; j * kWave < nv + h_out; ++j) {
+            const int i = j * kWave + lane - h_out;
+            if (i >= 0 && i < nv) {
+                u32x4 v = stage_v[i];
+#pragma unroll
+                for (int k = 0; k < kEpw; ++k)
+                    if (j == fj[k]) {
+                        if (lane == fl[k]) v = flip_byte(v, fq[k], fsh[k]);
+                    }
+                store16_wt(dst + i, v);
+            }
+        }
+    }
+    before = (unsigned)__builtin_amdgcn_readfirstlane((int)before);
+    if (before + 1 == expected) {        // wave-uniform: the last arriver publishes the workgroup's entries, one store per array
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");     // (this wave only: the others wait for nothing)
+        const int64_t left = B - wg_b0;
+        const int n_wg = (int)(left < kWpb * kEpw ? left : kWpb * kEpw);
+        if (lane < n_wg) {
+            const int v = mb_obj[lane];
+            const float r = mb_rew[lane];
+            if constexpr (SC1) {
+                asm volatile("global_store_dword %0, %1, off sc1" :: "v"(obj + wg_b0 + lane), "v"(v) : "memory");
+                asm volatile("global_store_dword %0, %1, off sc1" :: "v"(reward + wg_b0 + lane), "v"(r) : "memory");
+            } else {
+                obj[wg_b0 + lane] = v;
+                reward[wg_b0 + lane] = r;
+            }
+        }
+    }
+}
+
 typedef void (*KernFn)(const unsigned char*, unsigned char*, int64_t, int64_t, const int32_t*, const int32_t*, const int64_t*, int32_t*, float*);
 
 int main(int argc, char** argv) {
@@ -154,14 +396,24 @@ int main(int argc, char** argv) {
         rows_ok = (1 + 97 * j) % N != 0;                                              // never the node itself
         for (int j2 = 0; j2 < j && rows_ok; ++j2) rows_ok = (97 * (j - j2)) % N != 0;  // 20 distinct neighbours
     }
-    if (B <= 0 || B % kEpw || (kEpw * N) % 16 || !rows_ok || lds > 160 * 1024) {
+    if (B <= 0 || B % kEpw || (kEpw * N) % 16 || !rows_ok || lds + kMailbox > 160 * 1024) {
         fprintf(stderr, "need B a multiple of 4, 4 N a multiple of 16, an N at which i + 1 + 97 j mod N (j < 20) are 20 nodes other "
                         "than i, and 4 staged runs within 160 KB of LDS\n");
         return 1;
     }
-    const KernFn K[5] = {k_rung<0>, k_rung<1>, k_rung<2>, k_rung<3>, k_rung<4>};
-    const char* NAME[5] = {"a  copy only", "b  + action read, reward write", "c  + obj read-modify-write after the run",
-                           "d  + rowptr -> col chain, gather, flip after the run (serial per env)", "e  the work of d, operands requested beside the run"};
+    constexpr int NR = 11;
+    const KernFn K[NR] = {k_rung<0>, k_rung<1>, k_rung<2>, k_rung<3>, k_rung<4>, k_rung_wg<5>, k_rung_wg<6>, k_rung_wg<7>, k_rung_wg<8>,
+                          k_rung_wg<9>, k_rung_wg<10>};
+    const char* NAME[NR] = {"a  copy only", "b  + action read, reward write", "c  + obj read-modify-write after the run",
+                           "d  + rowptr -> col chain, gather, flip after the run (serial per env)", "e  the work of d, operands requested beside the run",
+                            "f  e, obj / reward leave once per workgroup (LDS mailbox, last arriver stores)",
+                            "g  f, one wait for all gather reads, flip in registers in the store loop",
+                            "h  g, the publisher's stores write-through (sc1)",
+                            "i  e, one wait for all gather reads, flip = one LDS write of the byte read (vs e)",
+                            "j  i, the wave's obj / reward stores write-through (sc1)",
+                            "k  i, the store loop reads 8 pieces from LDS before it stores the first (vs i)"};
+    auto lds_of = [&](int r) { return r >= 5 && r <= 7 ? lds + kMailbox : lds; };
+    const int BELOW[NR] = {0, 0, 1, 2, 3, 4, 5, 6, 4, 8, 8};       // the rung each one is measured against
     for (auto k : K) CK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 
     // graph: node i's row = i + 1 + 97 j mod N, j = 0..19 (distinct and never i itself: checked above)
@@ -192,9 +444,9 @@ int main(int argc, char** argv) {
     {   // pass 0 of every rung against the host
         std::vector<int32_t> h_obj(B);
         std::vector<float> h_rew(B);
-        for (int r = 0; r < 5; ++r) {
+        for (int r = 0; r < NR; ++r) {
             CK(hipMemset(obj, 0, B * 4)); CK(hipMemset(reward, 0xff, B * 4)); CK(hipMemset(slot[1], 2, bytes));
-            hipLaunchKernelGGL(K[r], dim3(grid), dim3(kWpb * kWave), lds, 0, slot[0], slot[1], B, N, rowptr, col, action, obj, reward);
+            hipLaunchKernelGGL(K[r], dim3(grid), dim3(kWpb * kWave), lds_of(r), 0, slot[0], slot[1], B, N, rowptr, col, action, obj, reward);
             CK(hipDeviceSynchronize());
             CK(hipMemcpy(h_out.data(), slot[1], bytes, hipMemcpyDeviceToHost));
             CK(hipMemcpy(h_obj.data(), obj, B * 4, hipMemcpyDeviceToHost));
@@ -225,11 +477,11 @@ int main(int argc, char** argv) {
     }
     const int passes = 200;
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-    std::vector<float> us[5];
+    std::vector<float> us[NR];
     for (int rep = 0; rep < 5; ++rep)
-        for (int r = 0; r < 5; ++r) {
+        for (int r = 0; r < NR; ++r) {
             auto pass = [&](int k) {
-                hipLaunchKernelGGL(K[r], dim3(grid), dim3(kWpb * kWave), lds, 0, slot[k % S], slot[(k + 1) % S], B, N, rowptr, col,
+                hipLaunchKernelGGL(K[r], dim3(grid), dim3(kWpb * kWave), lds_of(r), 0, slot[k % S], slot[(k + 1) % S], B, N, rowptr, col,
                                    action + (size_t)(k % NA) * B, obj, reward);
             };
             for (int k = 0; k < 16; ++k) pass(k);
@@ -243,14 +495,17 @@ int main(int argc, char** argv) {
         }
     printf("B = %lld, N = %lld bytes, EPW = %d, degree %d: slot %.1f MB, %u workgroups; %d passes per timing, 5 interleaved rounds\n",
            (long long)B, (long long)N, kEpw, kDeg, bytes / 1e6, grid, passes);
-    printf("%-78s %8s %8s %8s %9s %9s\n", "rung", "us min", "us med", "us max", "vs prev", "vs a");
-    float prev = 0, base = 0;
-    for (int r = 0; r < 5; ++r) {
+    printf("%-78s %8s %8s %8s %9s %9s %7s %8s\n", "rung", "us min", "us med", "us max", "vs below", "vs a", "spread", "wg / CU");
+    float med[NR] = {0}, base = 0;
+    for (int r = 0; r < NR; ++r) {
         auto t = us[r];
         std::sort(t.begin(), t.end());
         if (r == 0) base = t[2];
-        printf("%-78s %8.2f %8.2f %8.2f %+9.2f %+9.2f\n", NAME[r], t[0], t[2], t[4], r ? t[2] - prev : 0.f, t[2] - base);
-        prev = t[2];
+        int per_cu = 0;     // resident workgroups per CU at this rung's LDS size
+        CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)K[r], kWpb * kWave, lds_of(r)));
+        printf("%-78s %8.2f %8.2f %8.2f %+9.2f %+9.2f %7.2f %8d\n", NAME[r], t[0], t[2], t[4], r ? t[2] - med[BELOW[r]] : 0.f, t[2] - base,
+               t[4] - t[0], per_cu);
+        med[r] = t[2];
     }
     return 0;
 }
