@@ -379,6 +379,35 @@ int rls_rand_spins(uint8_t* x, int64_t B, int64_t N, uint64_t seed, int64_t env_
 int rls_rand_spins_repeats(uint8_t* x, int64_t R, int64_t S, int64_t N, const uint64_t* repeat_seeds, int64_t env_offset,
                            void* stream);
 
+/* [host] 1 when rls_sub_set_sampling runs S sims x N nodes x R repeats, else 0 (additive: the ABI stays v12).  The limits:
+ *   RLS_SUB_SET_SAMPLING_MAX_NODES  a workgroup keeps one sim's determinism row (uint32 [N]), two copies of its start row (N bytes
+ *                                   each, rounded up to 16, + 16) and the selected nodes (uint16 [N]) in LDS beside 1040 bytes of
+ *                                   scratch: about 8 N <= 160 KB, N <= 20 344 (G70's 10^4 nodes take 81 KB);
+ *   1 <= R < 2^31 (the repeat is a 32-bit counter of the generator), 0 <= S < 2^31, top_k >= 0, R S N within int64. */
+#define RLS_SUB_SET_SAMPLING_MAX_NODES 20344
+int rls_sub_set_sampling_supported(int64_t S, int64_t N, int64_t R, int64_t top_k);
+
+/* sub_set_sampling(probs, start_xs, num_repeats, top_k)  methods/L2A/transformer.py:335-353: the candidates of one policy step
+ * (L2A/demo_instance.py:148, demo_distribution.py:160, transformer.py:385) in ONE launch.  Per sim s, with k = min(top_k, N):
+ *     det[n] = |probs[s, n] - 0.5|                         one float32 subtraction, exact
+ *     selected = the k nodes with the smallest det         (the reference's topk(largest=False); a NaN det orders above every
+ *                                                          number, as in torch.topk)
+ *     xs_out[r S + s, n] = u(r, s, n) < det[n]  at a selected node, start_xs[s, n] elsewhere        for r = 0 .. R - 1
+ *     probs_out[s, n]   = probs[s, n]  at a selected node, (probs[s, n] < 0.5 ? 1 : 0) elsewhere
+ * Both quirks are the reference's: the Bernoulli parameter is the determinism, not the probability, and the unselected
+ * probabilities come back as 1 below 0.5 and 0 from it on (also for NaN).  Probabilities outside [0, 1] are taken as they are.
+ * TIES: where several nodes share the det value at the selection boundary the LOWER node index is selected (torch.topk leaves
+ * this unspecified); every NaN counts as the same value.  top_k = 0 copies start_xs R times; top_k >= N selects every node.
+ * probs f32 [S, N], start_xs uint8 [S, N] (copied as it is), xs_out uint8 [R S, N] (any byte alignment; written in 16-byte pieces),
+ * probs_out f32 [S, N] or NULL; no input is modified and no output may alias an input.
+ * uniforms f32 [R S, N] indexed (row, node) -- only the selected entries are read -- or NULL: the counter-based generator of the
+ * ISCO steps (murmur3 finaliser, 24 bits to [0, 1)) keyed by (seed, repeat r, env_offset + s, node), so that a rank holding sims
+ * [off, off + S_local) of a batch and passing env_offset = off writes exactly its rows (r, s) of the one-process result.
+ * The grid is sims x chunks of repeats; every workgroup redoes its sim's selection (a radix select over the N keys in LDS) and
+ * patches the row it keeps on chip at the selected nodes only.  RLS_EUNSUPPORTED outside rls_sub_set_sampling_supported, before
+ * any launch. */
+int rls_sub_set_sampling(const float* probs, const uint8_t* start_xs, int64_t S, int64_t N, int64_t R, int64_t top_k,
+                         const float* uniforms, uint64_t seed, int64_t env_offset, uint8_t* xs_out, float* probs_out, void* stream);
 
 /* uniform actions in [0, N) from the same generator (bench / MCMC proposals). */
 int rls_rand_actions(int64_t* action, int64_t B, int64_t N, uint64_t seed, uint64_t step,

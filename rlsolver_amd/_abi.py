@@ -109,6 +109,7 @@ SIGNATURES = {
     "rls_rand_spins": [_P, _I64, _I64, _U64, _I64, _P],
     "rls_rand_spins_repeats": [_P, _I64, _I64, _I64, _P, _I64, _P],
     "rls_rand_actions": [_P, _I64, _I64, _U64, _U64, _I64, _P],
+    "rls_sub_set_sampling": [_P, _P, _I64, _I64, _I64, _I64, _P, _U64, _I64, _P, _P, _P],
     "rls_spin_observation": [_SE, _P, C.c_int32, _INT, _I64, C.c_int32, _I64, _P, _I64, C.c_int32, _P, _P],
     "rls_spin_materialize": [_SE, _INT, _I64, _I64, C.c_int32, _P, _I64, _P],
     "rls_rand_couplings": [_P, _INT, _I64, _I64, C.c_int32, _F64, C.c_int32, C.c_int32, _U64, _I64, _P],
@@ -163,6 +164,7 @@ PLAIN = {"rls_version": ([], _INT), "rls_device_count": ([], _INT), "rls_last_er
          "rls_maxsat_local_search_supported": ([_I64, _I64, _P, _P], _INT),
          "rls_cheeger_local_search_supported": ([_I64, _I64, _I64, _P], _INT),
          "rls_maxcut_edge_local_search_supported": ([_I64, _I64, _I64, _I64, _I64, _P], _INT),
+         "rls_sub_set_sampling_supported": ([_I64, _I64, _I64, _I64], _INT),
          "rls_maxcut_ls_rounds_supported": ([_G, C.c_int32], _INT),
          "rls_maxcut_node_stats_form": ([_G, _I64, C.c_int32], _INT),
          "rls_mcpg_metro_max_rounds": ([_I64, C.c_int32], _I64),

@@ -3,6 +3,7 @@
 // unit is plain C++17, compiled into librlsolver_hip.so with the rest AND, on its own, with
 // -fsanitize=address,undefined by tests/test_sanitize.py (tools/host_sanitize.cpp drives it over random graphs).
 #include "rls_host.h"
+#include "rls_subset_plan.h"
 #include <cstdarg>
 #include <cstdio>
 #include <algorithm>
@@ -492,6 +493,9 @@ int rls_mcpg_visit_levels(const int32_t* rowptr, const int32_t* col, int64_t N, 
     *total = 2 * half;
     return RLS_OK;
 }
+
+// ---- sub_set_sampling: the launcher's own test (rls_subset_plan.h), answered without a device
+int rls_sub_set_sampling_supported(int64_t S, int64_t N, int64_t R, int64_t top_k) { return rls::subset_supported(S, N, R, top_k) ? 1 : 0; }
 
 // ---- MaxSAT: level schedule of the sampler's sweep (include/rlsolver_hip.h: rls_maxsat_visit_levels)
 namespace rls {

@@ -406,6 +406,44 @@ void rand_spins_repeats(Tensor x, Tensor repeat_seeds, int64_t env_offset) {
     ok(rls_rand_spins_repeats((uint8_t*)p(x), x.size(0), x.size(1), x.size(2), (const uint64_t*)p(repeat_seeds), env_offset, cur_stream(x)),
        "rls_rand_spins_repeats");
 }
+// bytes of two contiguous tensors share an address
+inline bool overlaps(const Tensor& a, const Tensor& b) {
+    const char* a0 = (const char*)a.data_ptr();
+    const char* b0 = (const char*)b.data_ptr();
+    return a0 < b0 + b.nbytes() && b0 < a0 + a.nbytes();
+}
+void sub_set_sampling(const Tensor& probs, const Tensor& start_xs, int64_t R, int64_t top_k, const OptTensor& uniforms, int64_t seed,
+                      int64_t env_offset, Tensor xs_out, const OptTensor& probs_out) {
+    dev(probs, "probs", F32);
+    spin_bytes(start_xs, "start_xs", false);
+    spin_bytes(xs_out, "xs_out", false);
+    TORCH_CHECK(probs.dim() == 2 && probs.size(1) >= 1, "probs must be [S, N] with N >= 1, got ", probs.sizes());
+    const int64_t S = probs.size(0), N = probs.size(1);
+    shape2(start_xs, "start_xs", S, N);
+    TORCH_CHECK(R >= 1, "num_repeats must be >= 1, got ", R);
+    TORCH_CHECK(top_k >= 0, "top_k must be >= 0, got ", top_k);
+    TORCH_CHECK(env_offset >= 0, "env_offset must be >= 0, got ", env_offset);
+    TORCH_CHECK(S == 0 || R <= INT64_MAX / N / S, "R * S * N = ", R, " * ", S, " * ", N, " does not fit int64");
+    shape2(xs_out, "xs_out", R * S, N);
+    same_device(probs, start_xs, "start_xs");
+    same_device(probs, xs_out, "xs_out");
+    optdev(uniforms, "uniforms", F32);
+    if (uniforms.has_value()) { shape2(*uniforms, "uniforms", R * S, N); same_device(probs, *uniforms, "uniforms"); }
+    optdev(probs_out, "probs_out", F32);
+    if (probs_out.has_value()) { shape2(*probs_out, "probs_out", S, N); same_device(probs, *probs_out, "probs_out"); }
+    // workgroups re-read the inputs while others write the outputs: shared bytes would be a race, not an in-place form
+    TORCH_CHECK(!overlaps(xs_out, start_xs), "xs_out overlaps start_xs");
+    TORCH_CHECK(!overlaps(xs_out, probs), "xs_out overlaps probs");
+    if (uniforms.has_value()) TORCH_CHECK(!overlaps(xs_out, *uniforms), "xs_out overlaps uniforms");
+    if (probs_out.has_value()) {
+        TORCH_CHECK(!overlaps(*probs_out, probs) && !overlaps(*probs_out, start_xs) && !overlaps(*probs_out, xs_out),
+                    "probs_out overlaps another argument");
+        if (uniforms.has_value()) TORCH_CHECK(!overlaps(*probs_out, *uniforms), "probs_out overlaps uniforms");
+    }
+    RLS_GUARD(probs);
+    ok(rls_sub_set_sampling((const float*)p(probs), (const uint8_t*)p(start_xs), S, N, R, top_k, (const float*)p(uniforms), (uint64_t)seed,
+                            env_offset, (uint8_t*)p(xs_out), (float*)p(probs_out), cur_stream(probs)), "rls_sub_set_sampling");
+}
 void rand_actions(Tensor action, int64_t N, int64_t seed, int64_t step, int64_t env_offset) {
     dev(action, "action", I64);
     RLS_GUARD(action);
@@ -1137,6 +1175,7 @@ TORCH_LIBRARY(rlsolver_hip, m) {
     m.def("winner_unpack(Tensor msg, int N, Tensor(a!)? x_out, Tensor(b!)? index_out) -> ()");
     m.def("rand_spins(Tensor(a!) x, int seed, int env_offset) -> ()");
     m.def("rand_spins_repeats(Tensor(a!) x, Tensor repeat_seeds, int env_offset) -> ()");
+    m.def("sub_set_sampling(Tensor probs, Tensor start_xs, int R, int top_k, Tensor? uniforms, int seed, int env_offset, Tensor(a!) xs_out, Tensor(b!)? probs_out) -> ()");
     m.def("rand_actions(Tensor(a!) action, int N, int seed, int step, int env_offset) -> ()");
     m.def("rand_perms(Tensor(a!) perm, int seed, int env_offset) -> ()");
     m.def("spin_reset(int graph, int env, Tensor(a!) state, Tensor row_index, float max_local, int weight_sum) -> ()");
@@ -1219,6 +1258,7 @@ TORCH_LIBRARY_IMPL(rlsolver_hip, CUDA, m) {   // "CUDA" is the HIP dispatch key 
     m.impl("winner_unpack", &winner_unpack);
     m.impl("rand_spins", &rand_spins);
     m.impl("rand_spins_repeats", &rand_spins_repeats);
+    m.impl("sub_set_sampling", &sub_set_sampling);
     m.impl("rand_actions", &rand_actions);
     m.impl("rand_perms", &rand_perms);
     m.impl("spin_reset", &spin_reset);

@@ -444,6 +444,90 @@ def rand_actions(B: int, N: int, seed: int, step: int, device, env_offset: int =
     return out
 
 
+# ---- L2A: sub_set_sampling (rls_sub_set_sampling), the candidates of one policy step
+SUB_SET_SAMPLING_MAX_NODES = 20344      # RLS_SUB_SET_SAMPLING_MAX_NODES: what one sim's rows take of the LDS
+
+
+def sub_set_sampling_supported(S: int, N: int, R: int, top_k: int) -> bool:
+    """Whether the kernel covers the shape (the library's own test: the gate and the launcher cannot disagree)."""
+    return bool(_abi.lib().rls_sub_set_sampling_supported(int(S), int(N), int(R), int(top_k)))
+
+
+def _subset_mix(h: TEN) -> TEN:
+    """The murmur3 finaliser of csrc/rls_draw.h on int64 tensors that hold uint32 values."""
+    m = 0xFFFFFFFF
+    h = h ^ (h >> 16)
+    h = (h * 0x85EBCA6B) & m
+    h = h ^ (h >> 13)
+    h = (h * 0xC2B2AE35) & m
+    return h ^ (h >> 16)
+
+
+def sub_set_sampling_draws(seed: int, env_offset: int, R: int, S: int, nodes: TEN) -> TEN:
+    """f32 [R, S, k]: the uniforms the kernel draws for (seed, repeat r, env_offset + s, nodes[s, j]) -- csrc/rls_draw.h restated
+    as torch ops, for the path past the kernel's node limit (and for the tests that pin the kernel's draws)."""
+    dev, m = nodes.device, 0xFFFFFFFF
+    seed &= _U64_MASK
+    env = torch.arange(S, dtype=torch.int64, device=dev) + int(env_offset)
+    h0 = torch.tensor([(seed & m) ^ 0x9E3779B9], dtype=torch.int64, device=dev)
+    key = _subset_mix(_subset_mix(_subset_mix(h0) ^ (seed >> 32)) ^ (env & m))                              # isco_env_key  [S]
+    r = torch.arange(R, dtype=torch.int64, device=dev)
+    pos = _subset_mix(key[None, :] ^ (env >> 32)[None, :] ^ ((r * 0x9E3779B1) & m)[:, None])                 # isco_pos_key  [R, S]
+    bits = _subset_mix(pos[:, :, None] ^ ((nodes.to(torch.int64) * 0x85EBCA77) & m)[None, :, :])             # isco_draw_at, stream 0
+    return (bits >> 8).to(torch.float32) * (1.0 / 16777216.0)
+
+
+def sub_set_sampling_torch(probs: TEN, start_xs: TEN, num_repeats: int, top_k: int, uniforms: Optional[TEN] = None, seed: int = 0,
+                           env_offset: int = 0):
+    """The rule of rls_sub_set_sampling as torch ops on the device, ties to the lower node index and the kernel's own draws
+    included: what ``sub_set_sampling`` runs past the kernel's node limit.  -> (xs [R S, N], probs [S, N])."""
+    S, N = probs.shape
+    R, k = int(num_repeats), min(int(top_k), N)
+    det = (probs - 0.5).abs()
+    key = det.view(torch.int32)                                   # det >= 0: its bits order as integers; every NaN is one key on top
+    key = torch.where(det.isnan(), torch.full_like(key, 0x7FC00000), key)
+    order = (key.to(torch.int64) << 32) | torch.arange(N, dtype=torch.int64, device=probs.device)[None, :]   # distinct: (det, node)
+    nodes = torch.topk(order, k, dim=1, largest=False)[0] & 0xFFFFFFFF                                       # [S, k]
+    selected = torch.zeros((S, N), dtype=torch.bool, device=probs.device).scatter_(1, nodes, True)
+    probs_out = torch.where(selected, probs, probs.lt(0.5).to(probs.dtype))
+    xs = start_xs.repeat(R, 1)
+    if k and R * S:
+        ids = nodes[None, :, :].expand(R, S, k)
+        u = uniforms.view(R, S, N).gather(2, ids) if uniforms is not None else sub_set_sampling_draws(seed, env_offset, R, S, nodes)
+        bits = u < det.gather(1, nodes)[None, :, :]
+        xs.view(R, S, N).scatter_(2, ids, bits.to(xs.dtype))
+    return xs, probs_out
+
+
+def sub_set_sampling(probs: TEN, start_xs: TEN, num_repeats: int, top_k: int, uniforms: Optional[TEN] = None, seed: int = 0,
+                     env_offset: int = 0, out: Optional[TEN] = None):
+    """transformer.py:335-353 in one launch (include/rlsolver_hip.h: rls_sub_set_sampling) -> (xs [R S, N], probs [S, N]).
+    ``uniforms`` f32 [R S, N] replaces the draws (test hook); else they are keyed by (seed, repeat, env_offset + sim, node).
+    Past the kernel's node limit the same rule runs as torch ops (sub_set_sampling_torch)."""
+    _check(probs, "probs", (torch.float32,))
+    dev = probs.device
+    if probs.dim() != 2 or probs.shape[1] < 1:
+        raise ValueError(f"probs must be [S, N] with N >= 1, got {tuple(probs.shape)}")
+    S, N = probs.shape
+    R, top_k = int(num_repeats), int(top_k)
+    if R < 1 or top_k < 0:
+        raise ValueError(f"num_repeats must be >= 1 and top_k >= 0, got {R} and {top_k}")
+    _check(start_xs, "start_xs", _SPIN_DTYPES, dev, (S, N))
+    if uniforms is not None:
+        _check(uniforms, "uniforms", (torch.float32,), dev, (R * S, N))
+    if out is not None:
+        _check(out, "out", (start_xs.dtype,), dev, (R * S, N))
+    if not sub_set_sampling_supported(S, N, R, top_k):
+        xs, probs_out = sub_set_sampling_torch(probs, start_xs, R, top_k, uniforms, seed, env_offset)
+        if out is not None:
+            xs = out.copy_(xs)
+        return xs, probs_out
+    xs = torch.empty((R * S, N), dtype=start_xs.dtype, device=dev) if out is None else out
+    probs_out = torch.empty_like(probs)
+    _t.sub_set_sampling(probs, start_xs, R, top_k, uniforms, _s64(seed), int(env_offset), xs, probs_out)
+    return xs, probs_out
+
+
 # ---- PISCO_maxcut: the dense f16 product and the sampler step over it (rls_pisco_product / rls_pisco_step)
 def pisco_scratch_bytes(Np: int, B: int) -> int:
     return int(_abi.lib().rls_pisco_scratch_bytes(int(Np), int(B)))

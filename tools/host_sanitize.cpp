@@ -4,7 +4,7 @@
 // EXACTLY-sized heap buffers, built with -fsanitize=address,undefined by tests/test_sanitize.py.  Every builder runs
 // its sizing call first and then fills buffers of exactly that size, so a one-past-the-end write is an ASAN report;
 // structural invariants (every node scheduled once, levels respect the dependency order, ELL rows complete) are checked
-// on top.  The launch planners (csrc/rls_maxcut_plan.h, rls_tsp_plan.h, rls_isco_plan.h: host-only C++) run over random shapes beside them.  Exit code 0 = clean.  CPU only: sanitizers do not run on the GPU box.
+// on top.  The launch planners (csrc/rls_maxcut_plan.h, rls_tsp_plan.h, rls_isco_plan.h, rls_subset_plan.h: host-only C++) run over random shapes beside them.  Exit code 0 = clean.  CPU only: sanitizers do not run on the GPU box.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -17,6 +17,7 @@
 #include "rls_maxcut_plan.h"      // the MaxCut launch planner: host-only C++, so it runs under the sanitizers too
 #include "rls_tsp_plan.h"         // ... and the TSP one
 #include "rls_isco_plan.h"        // ... and the ISCO steps'
+#include "rls_subset_plan.h"      // ... and sub_set_sampling's
 
 #include "../oracle/oracle.h"
 
@@ -310,6 +311,41 @@ static void run_isco_plans(std::mt19937_64& rng) {
     }
 }
 
+// sub_set_sampling's planner over random (S, N, R, top_k, CUs), sizes up to past the node limit and the 32-bit counters: it refuses
+// exactly where rls_sub_set_sampling_supported says 0; a plan fits LDS, has a nonzero one-dimensional grid, and its chunks are
+// nonempty, disjoint and cover every repeat exactly once
+static void run_subset_plans(std::mt19937_64& rng) {
+    for (int it = 0; it < 64; ++it) {
+        const uint64_t f = rng();
+        int64_t S = (f & 7) == 0 ? (int64_t)(rng() % 3) : (int64_t)(rng() % (1 << 17));
+        int64_t N = it == 0 ? rls::kSubsetMaxN : (it == 1 ? rls::kSubsetMaxN + 1 : 1 + (int64_t)(rng() % ((f & 8) ? 40000 : 4200)));
+        int64_t R = (f & 48) == 0 ? 1 + (int64_t)(rng() % 40) : 1 + (int64_t)(rng() % 70000);
+        int64_t top_k = (int64_t)(rng() % (uint64_t)(N + 8));
+        if ((f & 0xF00) == 0) R = (f & 0x1000) ? (1ll << 31) : (int64_t)(rng() % 3) - 1;                  // past the counter | 0, -1
+        if ((f & 0xF000) == 0) { S = (1ll << 30) + (int64_t)(rng() % 7); R = (1ll << 30); N = 20000; }      // R S N past int64
+        if ((f & 0xF0000) == 0) top_k = -1 - (int64_t)(rng() % 5);
+        const int cus = 1 + (int)(rng() % 512);
+        const int sup = rls_sub_set_sampling_supported(S, N, R, top_k);
+        const rls::SubsetPlan p = rls::subset_plan(S, N, R, top_k, cus);
+        CHECK((p.err == RLS_OK) == (sup == 1) && (p.err == RLS_OK || p.err == RLS_EUNSUPPORTED), "subset plan S %lld N %lld R %lld k %lld: err %d, supported %d",
+              (long long)S, (long long)N, (long long)R, (long long)top_k, p.err, sup);
+        CHECK(sup == (S >= 0 && N >= 1 && N <= RLS_SUB_SET_SAMPLING_MAX_NODES && R >= 1 && R < (1ll << 31) && S < (1ll << 31) && top_k >= 0 &&
+                      (S == 0 || (__int128)R * S * N <= (__int128)INT64_MAX)), "subset supported S %lld N %lld R %lld k %lld: %d", (long long)S,
+              (long long)N, (long long)R, (long long)top_k, sup);
+        if (p.err != RLS_OK) continue;
+        CHECK(p.lds == rls::subset_lds_bytes(N) && p.lds <= (size_t)rls::kLdsBytes && (p.block == 256 || p.block == 512 || p.block == 1024) &&
+                  (size_t)rls::kLdsBytes / p.lds * (size_t)p.block >= 1024, "subset plan N %lld: lds %zu block %d", (long long)N, p.lds, p.block);
+        CHECK(p.repeats >= 1 && p.chunks >= 1 && (p.chunks - 1) * p.repeats < R && p.chunks * p.repeats >= R,
+              "subset plan R %lld: %lld chunks of %lld repeats", (long long)R, (long long)p.chunks, (long long)p.repeats);
+        std::vector<char> covered((size_t)R, 0);
+        if (R <= 4096)
+            for (int64_t c = 0; c < p.chunks; ++c)
+                for (int64_t r = c * p.repeats; r < std::min(R, (c + 1) * p.repeats); ++r) CHECK(!covered[(size_t)r]++, "repeat %lld twice", (long long)r);
+        if (R <= 4096) for (int64_t r = 0; r < R; ++r) CHECK(covered[(size_t)r] == 1, "repeat %lld not covered", (long long)r);
+        CHECK(S == 0 || (S * p.chunks >= 1 && S * p.chunks < (1ll << 31)), "subset grid %lld x %lld", (long long)S, (long long)p.chunks);
+    }
+}
+
 // the MaxSAT level schedule (rls_maxsat_visit_levels) over random formulas: k-SAT with repeated variables, long clauses, empty
 // clauses, a hub variable, weighted or not, a random visiting order -- sized, then filled into buffers of exactly that size; every
 // entry points inside the tile, every variable sits in exactly one lane, a buffer one word short is refused
@@ -373,6 +409,7 @@ int main(int argc, char** argv) {
         run_oracle(g, rng);
         for (int k = 0; k < 50; ++k) run_planners(rng);
         run_isco_plans(rng);
+        run_subset_plans(rng);
         run_maxsat(rng, it);
     }
     std::printf("host_sanitize: %d random graphs through the host builders and the C oracle, clean\n", iters);
