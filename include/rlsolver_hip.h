@@ -1055,6 +1055,64 @@ int rls_isco_tsp_step(const float* dist, int64_t N, const int32_t* nearest, int3
  * vs[src[k]] for k < K (dst and src disjoint: top_ids vs low_ids there).  xs uint8 [*, N], vs int64 or NULL. */
 int rls_copy_rows(uint8_t* xs, int64_t* vs, int64_t N, const int64_t* dst, const int64_t* src, int64_t K, void* stream);
 
+/* ---- The MaxCut env of S2V_PPO  methods/S2V_PPO/env.py: a batch of envs on DIFFERENT graphs (additive: the ABI stays v12).
+ * The batch is laid out like a torch_geometric Batch: env i owns nodes [ptr[i], ptr[i + 1]) of every per-node array, and ONE CSR by
+ * source over all nodes holds the edge-list entries as given (env.py:199 reads rows edge_index[0] == a and nothing else: a line
+ * listed twice counts twice, a loop (u, u) is an ordinary entry, a one-directional line stays one-directional); each row is sorted
+ * by destination (stable), columns are global node ids inside the row's own env.  All pointers are device memory; the struct lives
+ * on the host.  No scratch is needed. */
+typedef struct rls_s2vppo_env {
+    int64_t num_envs, total_nodes, max_nodes;   /* B, sum of N_i (< 2^31), the largest N_i (chooses the launch form) */
+    int64_t nnz, tenure, multiplier;            /* entries; config.tabu_tenure >= 0; config.episode_length_multiplier >= 1 */
+    const int64_t* ptr;        /* [B + 1] */
+    const int64_t* rowptr;     /* [total_nodes + 1] */
+    const int32_t* col;        /* [nnz] */
+    const float* w;            /* [nnz] */
+    const float* wtot;         /* [B, 3]: W = sum(w) / 2 (env.py:19), W + 1e-8 as float32 (env.py:119), and 1 when the graph's list equals
+                                * its transpose, weights included (the greedy reset then updates gains in O(deg) per flip), else 0 */
+    int8_t* z;                 /* [total_nodes] -1 | +1 */
+    float* delta;              /* [total_nodes] delta_cache: z_i * sum of w z_dst over i's row */
+    int32_t* last_flip;        /* [total_nodes] step count at the node's last flip: time_since_flip = step_count - last_flip */
+    int8_t* best_z;            /* [total_nodes] */
+    int32_t* counters;         /* [B, 4]: step_count, recorded basins, episodes begun, source of the start spins (0 z0, 1 random, 2 greedy) */
+    double* cut;               /* [B] current_cut (also the step's info['cut_value']) */
+    double* best_cut;          /* [B] */
+    int32_t* tabu;             /* [B, max(tenure, 1)] ring of the last `tenure` actions, slot (step - 1) % tenure */
+    int64_t* hash;             /* [B, 51]: ring of the last 50 state hashes (slot step % 50) and the current one */
+    int64_t* basins;           /* [multiplier * total_nodes]: env i records at most max_steps_i basins from multiplier * ptr[i] */
+    float* x;                  /* [total_nodes, 5] node features, rewritten in place (env.py:116-131) */
+    uint8_t* mask;             /* [total_nodes] valid_actions_mask (env.py:107-114) */
+} rls_s2vppo_env;
+
+/* [host] The launch rls_s2vppo_step / _reset make for B envs whose largest graph has max_nodes nodes (csrc/rls_s2vppo_plan.h):
+ * out[0] form (0: a wave per env, 1: a workgroup per env), out[1] threads per workgroup, out[2] envs per workgroup, out[3] workgroups. */
+int rls_s2vppo_launch_plan(int64_t B, int64_t max_nodes, int64_t* out);
+
+/* EnvMaxcut.step  S2V_PPO/env.py:140-206 for every env of the batch in ONE launch (train_ddp.py:117-139 loops over env objects).
+ * action int64 [B], LOCAL node ids.  Per env, in the reference's order: cut += delta[a] (:141-144); z[a] = -z[a]; delta[dst] +=
+ * 2 z[dst] z[a] w over a's row, entries of one destination added in list order by one lane (:197-205; a loop sees the new z[a]); THEN
+ * delta[a] = -delta[a] (:206); step_count, the tabu ring, last_flip (:150-156); `new` = the state's hash is not among the last 50
+ * (:159-160); reward in float64 (:163-183): (cut - best) / ((cut - best) + 0.1) if the cut beats the best (best_cut, best_z follow),
+ * - stag_punishment if not new, + 0.01 if every delta <= 0 and the hash is no recorded basin (it is then recorded); THEN the hash
+ * joins the history (:186); done = step_count >= multiplier * N (:188); x and mask are rewritten (:107-131).
+ * A state's identity is a 64-bit Zobrist hash (XOR of a fixed key(local node) over the nodes with z = +1); the reference compares
+ * Python hashes of the spin bytes.  Two different states of one episode collide with probability about 2^-64 per pair.
+ * reward f64 [B], done uint8 [B].  An action outside [0, N_i) leaves its env untouched and reports reward = NaN, as rls_maxcut_step
+ * does (the reference raises an IndexError); so does an env whose step_count has reached multiplier * N (done stays 1): the basin
+ * table holds one episode, reset it first.  No host read, no allocation: capturable in a HIP graph.
+ * The action's row is walked in strides of the group, but a run of equal destinations is added by ONE thread in list order: a row
+ * costs its longest run, not d / threads. */
+int rls_s2vppo_step(const rls_s2vppo_env* e, const int64_t* action, double stag_punishment, double* reward, uint8_t* done, void* stream);
+
+/* EnvMaxcut.reset  S2V_PPO/env.py:46-74 for the envs ids[0 .. num_ids) (distinct), or for all of them (ids NULL, num_ids = B), in ONE
+ * launch.  The start spins: z0 int8 [total_nodes] when given (test hook: only the listed envs' nodes are read); else greedy uint8 [B]
+ * when given chooses per env (1: from all-ones flip the node with the largest gain, ties to the lowest index, while that gain is > 0,
+ * at most N / 2 times :51-57 -- the gains follow a flip through the node's row when the list is its own transpose, else all are recomputed; 0: independent +-1 spins :49); else a coin decides.  Coin and spins come from the counter-based generator
+ * of the ISCO steps keyed by (seed, env_offset + env, the env's episode counter, node).  Then delta, cut = W / 2 - sum(z nb) / 4, best =
+ * cut, best_z = z, the hash; counters and rings start over; x and mask are written. */
+int rls_s2vppo_reset(const rls_s2vppo_env* e, const int64_t* ids, int64_t num_ids, const int8_t* z0, const uint8_t* greedy, uint64_t seed,
+                     int64_t env_offset, void* stream);
+
 /* B random permutations (random_gen_init_sample, env_ISCO.py:352-354). */
 int rls_rand_perms(int64_t* perm, int64_t B, int64_t N, uint64_t seed, int64_t env_offset,
                    void* stream);

@@ -109,6 +109,9 @@ SIGNATURES = {
     "rls_rand_spins": [_P, _I64, _I64, _U64, _I64, _P],
     "rls_rand_spins_repeats": [_P, _I64, _I64, _I64, _P, _I64, _P],
     "rls_rand_actions": [_P, _I64, _I64, _U64, _U64, _I64, _P],
+    "rls_s2vppo_step": [_P, _P, _F64, _P, _P, _P],
+    "rls_s2vppo_reset": [_P, _P, _I64, _P, _P, _U64, _I64, _P],
+    "rls_s2vppo_launch_plan": [_I64, _I64, _P],
     "rls_sub_set_sampling": [_P, _P, _I64, _I64, _I64, _I64, _P, _U64, _I64, _P, _P, _P],
     "rls_spin_observation": [_SE, _P, C.c_int32, _INT, _I64, C.c_int32, _I64, _P, _I64, C.c_int32, _P, _P],
     "rls_spin_materialize": [_SE, _INT, _I64, _I64, C.c_int32, _P, _I64, _P],

@@ -4,6 +4,7 @@
 // -fsanitize=address,undefined by tests/test_sanitize.py (tools/host_sanitize.cpp drives it over random graphs).
 #include "rls_host.h"
 #include "rls_subset_plan.h"
+#include "rls_s2vppo_plan.h"
 #include <cstdarg>
 #include <cstdio>
 #include <algorithm>
@@ -496,6 +497,15 @@ int rls_mcpg_visit_levels(const int32_t* rowptr, const int32_t* col, int64_t N, 
 
 // ---- sub_set_sampling: the launcher's own test (rls_subset_plan.h), answered without a device
 int rls_sub_set_sampling_supported(int64_t S, int64_t N, int64_t R, int64_t top_k) { return rls::subset_supported(S, N, R, top_k) ? 1 : 0; }
+
+// ---- S2V_PPO env: the launchers' own planner (rls_s2vppo_plan.h), answered without a device
+int rls_s2vppo_launch_plan(int64_t B, int64_t max_nodes, int64_t* out) {
+    if (!out) return rls::fail(RLS_EINVAL, "out is NULL");
+    const rls::S2vPlan p = rls::s2vppo_plan(B, max_nodes);
+    if (p.err != RLS_OK) return rls::fail(p.err, "s2vppo_launch_plan: B=%lld and max_nodes=%lld must be in [0, 2^31)", (long long)B, (long long)max_nodes);
+    out[0] = p.form; out[1] = p.block; out[2] = p.envs; out[3] = p.grid;
+    return RLS_OK;
+}
 
 // ---- MaxSAT: level schedule of the sampler's sweep (include/rlsolver_hip.h: rls_maxsat_visit_levels)
 namespace rls {

@@ -444,6 +444,77 @@ void sub_set_sampling(const Tensor& probs, const Tensor& start_xs, int64_t R, in
     ok(rls_sub_set_sampling((const float*)p(probs), (const uint8_t*)p(start_xs), S, N, R, top_k, (const float*)p(uniforms), (uint64_t)seed,
                             env_offset, (uint8_t*)p(xs_out), (float*)p(probs_out), cur_stream(probs)), "rls_sub_set_sampling");
 }
+// ---- the S2V_PPO env: the batch and its state travel as the tensors themselves, so that every shape is checked here
+rls_s2vppo_env s2v_env(const Tensor& ptr, const Tensor& rowptr, const Tensor& col, const Tensor& w, const Tensor& wtot, const Tensor& z,
+                       const Tensor& delta, const Tensor& last_flip, const Tensor& best_z, const Tensor& counters, const Tensor& cut,
+                       const Tensor& best_cut, const Tensor& tabu, const Tensor& hash, const Tensor& basins, const Tensor& x, const Tensor& mask,
+                       int64_t max_nodes, int64_t tenure, int64_t multiplier) {
+    dev(ptr, "ptr", I64);
+    TORCH_CHECK(ptr.dim() == 1 && ptr.numel() >= 1, "ptr must be [B + 1], got ", ptr.sizes());
+    const int64_t B = ptr.numel() - 1;
+    dev(z, "z", at::kChar);
+    TORCH_CHECK(z.dim() == 1, "z must be [total_nodes], got ", z.sizes());
+    const int64_t T = z.numel();
+    TORCH_CHECK(T < (1ll << 31), "total_nodes = ", T, " must stay below 2^31");
+    TORCH_CHECK(tenure >= 0 && tenure < (1ll << 31), "tabu_tenure must be in [0, 2^31), got ", tenure);
+    TORCH_CHECK(multiplier >= 1 && multiplier < (1ll << 31) && multiplier * T < (1ll << 31),
+                "episode_length_multiplier must be >= 1 with multiplier * total_nodes < 2^31, got ", multiplier);
+    TORCH_CHECK(max_nodes >= 0 && max_nodes <= T, "max_nodes must be in [0, total_nodes = ", T, "], got ", max_nodes);
+    dev(rowptr, "rowptr", I64); count(rowptr, "rowptr", T + 1);
+    dev(col, "col", I32);
+    TORCH_CHECK(col.dim() == 1, "col must be [nnz], got ", col.sizes());
+    dev(w, "w", F32); count(w, "w", col.numel());
+    dev(wtot, "wtot", F32); shape2(wtot, "wtot", B, 3);
+    dev(delta, "delta", F32); count(delta, "delta", T);
+    dev(last_flip, "last_flip", I32); count(last_flip, "last_flip", T);
+    dev(best_z, "best_z", at::kChar); count(best_z, "best_z", T);
+    dev(counters, "counters", I32); shape2(counters, "counters", B, 4);
+    dev(cut, "cut", F64); count(cut, "cut", B);
+    dev(best_cut, "best_cut", F64); count(best_cut, "best_cut", B);
+    dev(tabu, "tabu", I32); shape2(tabu, "tabu", B, tenure > 1 ? tenure : 1);
+    dev(hash, "hash", I64); shape2(hash, "hash", B, 51);
+    dev(basins, "basins", I64); count(basins, "basins", multiplier * T);
+    dev(x, "x", F32); shape2(x, "x", T, 5);
+    spin_bytes(mask, "mask", false); count(mask, "mask", T);
+    const Tensor* all[] = {&rowptr, &col, &w, &wtot, &z, &delta, &last_flip, &best_z, &counters, &cut, &best_cut, &tabu, &hash, &basins, &x, &mask};
+    const char* names[] = {"rowptr", "col", "w", "wtot", "z", "delta", "last_flip", "best_z", "counters", "cut", "best_cut", "tabu", "hash", "basins", "x", "mask"};
+    for (int i = 0; i < 16; ++i) same_device(ptr, *all[i], names[i]);
+    rls_s2vppo_env e{};
+    e.num_envs = B; e.total_nodes = T; e.max_nodes = max_nodes; e.nnz = col.numel(); e.tenure = tenure; e.multiplier = multiplier;
+    e.ptr = (const int64_t*)p(ptr); e.rowptr = (const int64_t*)p(rowptr); e.col = (const int32_t*)p(col); e.w = (const float*)p(w);
+    e.wtot = (const float*)p(wtot); e.z = (int8_t*)p(z); e.delta = (float*)p(delta); e.last_flip = (int32_t*)p(last_flip);
+    e.best_z = (int8_t*)p(best_z); e.counters = (int32_t*)p(counters); e.cut = (double*)p(cut); e.best_cut = (double*)p(best_cut);
+    e.tabu = (int32_t*)p(tabu); e.hash = (int64_t*)p(hash); e.basins = (int64_t*)p(basins); e.x = (float*)p(x); e.mask = (uint8_t*)p(mask);
+    return e;
+}
+void s2vppo_step(const Tensor& ptr, const Tensor& rowptr, const Tensor& col, const Tensor& w, const Tensor& wtot, Tensor z, Tensor delta,
+                 Tensor last_flip, Tensor best_z, Tensor counters, Tensor cut, Tensor best_cut, Tensor tabu, Tensor hash, Tensor basins, Tensor x,
+                 Tensor mask, int64_t max_nodes, int64_t tenure, int64_t multiplier, const Tensor& action, double stag_punishment, Tensor reward,
+                 Tensor done) {
+    const rls_s2vppo_env e = s2v_env(ptr, rowptr, col, w, wtot, z, delta, last_flip, best_z, counters, cut, best_cut, tabu, hash, basins, x, mask,
+                                     max_nodes, tenure, multiplier);
+    dev(action, "action", I64); count(action, "action", e.num_envs); same_device(ptr, action, "action");
+    dev(reward, "reward", F64); count(reward, "reward", e.num_envs); same_device(ptr, reward, "reward");
+    spin_bytes(done, "done", false); count(done, "done", e.num_envs); same_device(ptr, done, "done");
+    RLS_GUARD(ptr);
+    ok(rls_s2vppo_step(&e, (const int64_t*)p(action), stag_punishment, (double*)p(reward), (uint8_t*)p(done), cur_stream(ptr)), "rls_s2vppo_step");
+}
+void s2vppo_reset(const Tensor& ptr, const Tensor& rowptr, const Tensor& col, const Tensor& w, const Tensor& wtot, Tensor z, Tensor delta,
+                  Tensor last_flip, Tensor best_z, Tensor counters, Tensor cut, Tensor best_cut, Tensor tabu, Tensor hash, Tensor basins, Tensor x,
+                  Tensor mask, int64_t max_nodes, int64_t tenure, int64_t multiplier, const OptTensor& ids, const OptTensor& z0,
+                  const OptTensor& greedy, int64_t seed, int64_t env_offset) {
+    const rls_s2vppo_env e = s2v_env(ptr, rowptr, col, w, wtot, z, delta, last_flip, best_z, counters, cut, best_cut, tabu, hash, basins, x, mask,
+                                     max_nodes, tenure, multiplier);
+    optdev(ids, "ids", I64);
+    if (ids.has_value()) { TORCH_CHECK(ids->dim() == 1, "ids must be one-dimensional, got ", ids->sizes()); same_device(ptr, *ids, "ids"); }
+    optdev(z0, "z0", at::kChar);
+    if (z0.has_value()) { count(*z0, "z0", e.total_nodes); same_device(ptr, *z0, "z0"); }
+    if (greedy.has_value()) { spin_bytes(*greedy, "greedy", false); count(*greedy, "greedy", e.num_envs); same_device(ptr, *greedy, "greedy"); }
+    TORCH_CHECK(env_offset >= 0, "env_offset must be >= 0, got ", env_offset);
+    RLS_GUARD(ptr);
+    ok(rls_s2vppo_reset(&e, (const int64_t*)p(ids), ids.has_value() ? ids->numel() : e.num_envs, (const int8_t*)p(z0), (const uint8_t*)p(greedy),
+                        (uint64_t)seed, env_offset, cur_stream(ptr)), "rls_s2vppo_reset");
+}
 void rand_actions(Tensor action, int64_t N, int64_t seed, int64_t step, int64_t env_offset) {
     dev(action, "action", I64);
     RLS_GUARD(action);
@@ -1176,6 +1247,8 @@ TORCH_LIBRARY(rlsolver_hip, m) {
     m.def("rand_spins(Tensor(a!) x, int seed, int env_offset) -> ()");
     m.def("rand_spins_repeats(Tensor(a!) x, Tensor repeat_seeds, int env_offset) -> ()");
     m.def("sub_set_sampling(Tensor probs, Tensor start_xs, int R, int top_k, Tensor? uniforms, int seed, int env_offset, Tensor(a!) xs_out, Tensor(b!)? probs_out) -> ()");
+    m.def("s2vppo_step(Tensor ptr, Tensor rowptr, Tensor col, Tensor w, Tensor wtot, Tensor(a!) z, Tensor(b!) delta, Tensor(c!) last_flip, Tensor(d!) best_z, Tensor(e!) counters, Tensor(f!) cut, Tensor(g!) best_cut, Tensor(h!) tabu, Tensor(i!) hash, Tensor(j!) basins, Tensor(k!) x, Tensor(l!) mask, int max_nodes, int tenure, int multiplier, Tensor action, float stag_punishment, Tensor(m!) reward, Tensor(n!) done) -> ()");
+    m.def("s2vppo_reset(Tensor ptr, Tensor rowptr, Tensor col, Tensor w, Tensor wtot, Tensor(a!) z, Tensor(b!) delta, Tensor(c!) last_flip, Tensor(d!) best_z, Tensor(e!) counters, Tensor(f!) cut, Tensor(g!) best_cut, Tensor(h!) tabu, Tensor(i!) hash, Tensor(j!) basins, Tensor(k!) x, Tensor(l!) mask, int max_nodes, int tenure, int multiplier, Tensor? ids, Tensor? z0, Tensor? greedy, int seed, int env_offset) -> ()");
     m.def("rand_actions(Tensor(a!) action, int N, int seed, int step, int env_offset) -> ()");
     m.def("rand_perms(Tensor(a!) perm, int seed, int env_offset) -> ()");
     m.def("spin_reset(int graph, int env, Tensor(a!) state, Tensor row_index, float max_local, int weight_sum) -> ()");
@@ -1259,6 +1332,8 @@ TORCH_LIBRARY_IMPL(rlsolver_hip, CUDA, m) {   // "CUDA" is the HIP dispatch key 
     m.impl("rand_spins", &rand_spins);
     m.impl("rand_spins_repeats", &rand_spins_repeats);
     m.impl("sub_set_sampling", &sub_set_sampling);
+    m.impl("s2vppo_step", &s2vppo_step);
+    m.impl("s2vppo_reset", &s2vppo_reset);
     m.impl("rand_actions", &rand_actions);
     m.impl("rand_perms", &rand_perms);
     m.impl("spin_reset", &spin_reset);
