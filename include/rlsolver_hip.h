@@ -363,7 +363,9 @@ int rls_key_unpack(const int64_t* key, int32_t rank_bits, int64_t world, int as_
  * whose low code survived in the reduced key[0] writes msg = { (index[0] + env_offset) as 8 little-endian bytes | its row xs[index[0]]
  * bit-packed, bit k of byte j = x[8 j + k] }, every other rank (and a rank with B = 0) zeros -- msg uint8 [8 + ceil(N / 8)].  A
  * SUM all-reduce of msg is then the winner's message on every rank, and rls_winner_unpack turns it into x_out uint8 [N] (may be
- * NULL) and index_out int64[1] (may be NULL).  xs uint8 [B, N] 0|1; B == 1: the row itself (index only supplies the env id). */
+ * NULL) and index_out int64[1] (may be NULL).  xs uint8 [B, N] 0|1; B == 1: the row itself (index only supplies the env id).
+ * index[0] is read on the device: with B > 1 a value outside [0, B) is "not mine" -- the rank writes zeros, as a rank without envs
+ * does -- and never an address outside xs. */
 int rls_winner_message(const uint8_t* xs, int64_t B, int64_t N, const int64_t* index, const int64_t* key, int32_t rank_bits,
                        int64_t my_low_code, int64_t env_offset, uint8_t* msg, void* stream);
 int rls_winner_unpack(const uint8_t* msg, int64_t N, uint8_t* x_out, int64_t* index_out, void* stream);
@@ -669,7 +671,8 @@ int rls_mcpg_visit_levels(const int32_t* rowptr, const int32_t* col, int64_t N, 
  * block [chain_ids, host; NULL = identity], pass, position); coins uint64 [num_ls * N, ceil(C / 64)] -- bit c % 64 of word [pass * N + pos, c / 64] =
  * "u < 1/2" for chain c -- replaces them for tests).  Same outputs as rls_mcpg_local_search; xs_out is float32
  * node-major (out_spin_bytes = 4) or bit-packed (0; then xs_out may alias a bit-packed xs_in).  C_in: as in
- * rls_mcpg_metro_rounds. */
+ * rls_mcpg_metro_rounds.  The caller's contract, like a tour: lv_data holds the `total` entries that lv_ptr's offsets name -- the
+ * entry point is told num_groups, not that length, and does not check it. */
 int rls_mcpg_local_search_levels(const rls_graph* g, const void* xs_in, int spin_bytes, int64_t C_in, void* xs_out,
                                  int out_spin_bytes, int64_t C, const int32_t* lv_ptr, const int32_t* lv_data,
                                  int64_t num_groups, int64_t num_ls, const uint64_t* coins, uint64_t seed, float* expected,
@@ -804,7 +807,9 @@ int rls_maxsat_local_search_supported(int64_t nvar, int64_t weight_sum, int64_t*
  * max_lit(s_v neg) = +w for a satisfied clause, -w for an unsatisfied one, 0 for an empty one (:272-274).  The reference's
  * res = (S + K) / 2 is rls_mcpg_pick_best's (num_edges - expected) / 2 with num_edges := K, its first argmax of res that
  * kernel's first argmin of expected: K never enters this launch.  lit must not be NULL when M > 0, also where every clause is
- * empty (it is then never read). */
+ * empty (it is then never read). 
+ * The caller's contract, like a tour: lv_data holds the `total` entries of rls_maxsat_visit_levels and lit the clause_ptr[M]
+ * literals -- the entry point is told num_groups and M, not those lengths, and does not check them. */
 int rls_maxsat_local_search(const void* xs_in, int64_t C_in, void* xs_out, int out_spin_bytes, int64_t C, int64_t nvar,
                             const int32_t* lv_ptr, const int32_t* lv_data, int64_t num_groups, int64_t num_ls,
                             const uint64_t* coins, uint64_t seed, const int32_t* clause_ptr, const int32_t* lit,
@@ -1054,6 +1059,10 @@ int rls_isco_tsp_step(const float* dist, int64_t N, const int32_t* nearest, int3
 /* The row moves of evolutionary_replacement  methods/util.py:87-94:  xs[dst[k]] = xs[src[k]], vs[dst[k]] =
  * vs[src[k]] for k < K (dst and src disjoint: top_ids vs low_ids there).  xs uint8 [*, N], vs int64 or NULL. */
 int rls_copy_rows(uint8_t* xs, int64_t* vs, int64_t N, const int64_t* dst, const int64_t* src, int64_t K, void* stream);
+/* The same moves with the row count (additive: the ABI stays v12).  dst and src are read on the device: a move with dst[k] or
+ * src[k] outside [0, B) is skipped -- xs, vs and everything around them stay as they were -- where rls_copy_rows, which is not
+ * told B, can only skip a negative index.  xs uint8 [B, N], vs int64 [B] or NULL.  Call this one. */
+int rls_copy_rows_bounded(uint8_t* xs, int64_t* vs, int64_t B, int64_t N, const int64_t* dst, const int64_t* src, int64_t K, void* stream);
 
 /* ---- The MaxCut env of S2V_PPO  methods/S2V_PPO/env.py: a batch of envs on DIFFERENT graphs (additive: the ABI stays v12).
  * The batch is laid out like a torch_geometric Batch: env i owns nodes [ptr[i], ptr[i + 1]) of every per-node array, and ONE CSR by

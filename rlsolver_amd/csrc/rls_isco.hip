@@ -949,13 +949,16 @@ __global__ __launch_bounds__(256) void k_isco_tsp_step(IscoTspArgs a) {
 // K10' evolutionary_replacement  methods/util.py:87-94, the row moves: xs[dst[k]] = xs[src[k]], vs likewise.
 // The reference's  xs[replace_ids] = xs[low_ids]  gathers the right-hand side first; dst and src are disjoint
 // by construction (top_ids vs low_ids), so the copy may run in place.  One wave per moved row, 16-byte lanes.
-__global__ __launch_bounds__(256) void k_copy_rows(uint8_t* __restrict__ xs, int64_t* __restrict__ vs, int64_t N,
+// dst and src come from device memory: a move with either index outside [0, B) is skipped (the unsigned compare also
+// catches a negative index), so no index can turn into an address outside xs / vs.
+__global__ __launch_bounds__(256) void k_copy_rows(uint8_t* __restrict__ xs, int64_t* __restrict__ vs, int64_t B, int64_t N,
                                                    const int64_t* __restrict__ dst, const int64_t* __restrict__ src,
                                                    int64_t K, int vec) {
     const int lane = threadIdx.x & (kWave - 1);
     const int64_t k = (int64_t)blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
     if (k >= K) return;
     const int64_t d = dst[k], s = src[k];
+    if ((uint64_t)d >= (uint64_t)B || (uint64_t)s >= (uint64_t)B) return;
     if (vec) {
         const u32x4* sp = reinterpret_cast<const u32x4*>(xs + s * N);
         u32x4* dp = reinterpret_cast<u32x4*>(xs + d * N);
@@ -1113,13 +1116,20 @@ int rls_isco_tsp_step(const float* dist, int64_t N, const int32_t* nearest, int3
     return check_launch("k_isco_tsp_step");
 }
 
-int rls_copy_rows(uint8_t* xs, int64_t* vs, int64_t N, const int64_t* dst, const int64_t* src, int64_t K, void* stream) {
-    RLS_REQUIRE(N > 0 && K >= 0, RLS_EINVAL, "bad sizes");
-    if (K == 0) return RLS_OK;
+int rls_copy_rows_bounded(uint8_t* xs, int64_t* vs, int64_t B, int64_t N, const int64_t* dst, const int64_t* src, int64_t K, void* stream) {
+    RLS_REQUIRE(B >= 0 && N > 0 && K >= 0, RLS_EINVAL, "bad sizes B=%lld N=%lld K=%lld", (long long)B, (long long)N, (long long)K);
+    RLS_REQUIRE(B <= INT64_MAX / N, RLS_EINVAL, "B * N = %lld * %lld does not fit int64", (long long)B, (long long)N);
+    if (K == 0 || B == 0) return RLS_OK;
     RLS_REQUIRE(xs && dst && src, RLS_EINVAL, "NULL pointer");
     const int vec = ((((uintptr_t)xs) & 15) == 0 && N % 16 == 0) ? 1 : 0;
-    hipLaunchKernelGGL(k_copy_rows, dim3((unsigned)ceil_div(K, 4)), dim3(256), 0, as_stream(stream), xs, vs, N, dst, src, K, vec);
+    hipLaunchKernelGGL(k_copy_rows, dim3((unsigned)ceil_div(K, 4)), dim3(256), 0, as_stream(stream), xs, vs, B, N, dst, src, K, vec);
     return check_launch("k_copy_rows");
+}
+
+// the first form: it is not told how many rows xs has, so only a negative index (or one past what int64 addresses) is skipped
+int rls_copy_rows(uint8_t* xs, int64_t* vs, int64_t N, const int64_t* dst, const int64_t* src, int64_t K, void* stream) {
+    RLS_REQUIRE(N > 0 && K >= 0, RLS_EINVAL, "bad sizes");
+    return rls_copy_rows_bounded(xs, vs, INT64_MAX / N, N, dst, src, K, stream);
 }
 
 }  // extern "C"

@@ -130,12 +130,13 @@ __global__ void k_key_unpack(const int64_t* __restrict__ key, int rank_bits, int
 // C2 without a host read (round 6): after the key's all-reduce every rank writes ITS candidate message -- the winner (the rank whose
 // low code survived in the reduced key) its global env index and its row bit-packed, everyone else zeros -- and a SUM all-reduce of
 // the messages is the winner's message on every rank.  msg: uint8 [8 + ceil(N / 8)] = { global index, little endian | bit k of
-// byte j = x[8 j + k] }.  xs is this rank's [B, N] (row index[0]) or a single row (B = 1, index ignored).
+// byte j = x[8 j + k] }.  xs is this rank's [B, N] (row index[0]) or a single row (B = 1, index ignored).  index[0] comes from
+// device memory: outside [0, B) it names no row of this rank, which then writes zeros like a rank that did not win.
 __global__ __launch_bounds__(256) void k_winner_message(const uint8_t* __restrict__ xs, int64_t B, int64_t N, const int64_t* __restrict__ index,
                                                         const int64_t* __restrict__ key, int rank_bits, int64_t my_low_code,
                                                         int64_t env_offset, uint8_t* __restrict__ msg, int64_t msg_bytes) {
-    const bool mine = xs != nullptr && (key[0] & ((1ll << rank_bits) - 1)) == my_low_code;
     const int64_t li = (B > 1 && index) ? index[0] : 0;
+    const bool mine = xs != nullptr && (uint64_t)li < (uint64_t)B && (key[0] & ((1ll << rank_bits) - 1)) == my_low_code;
     for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < msg_bytes; j += (int64_t)gridDim.x * blockDim.x) {
         uint8_t v = 0;
         if (mine) {

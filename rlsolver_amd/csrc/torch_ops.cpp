@@ -61,6 +61,18 @@ inline void at_least(const Tensor& t, const char* name, int64_t n) {
 inline void same_device(const Tensor& a, const Tensor& b, const char* name) {
     TORCH_CHECK(a.device() == b.device(), name, " is on ", b.device(), ", expected ", a.device());
 }
+// every (name, tensor) pair after `a` lives on a's device; an absent optional tensor is skipped.  Each op with more than one device
+// tensor has this ONE line over all of them, so that no kernel is launched on one device with a pointer into another
+inline void on_device_of(const Tensor&) {}
+template <class... Rest> void on_device_of(const Tensor& a, const char* name, const Tensor& b, const Rest&... rest);
+template <class... Rest> void on_device_of(const Tensor& a, const char* name, const OptTensor& b, const Rest&... rest) {
+    if (b.has_value()) same_device(a, *b, name);
+    on_device_of(a, rest...);
+}
+template <class... Rest> void on_device_of(const Tensor& a, const char* name, const Tensor& b, const Rest&... rest) {
+    same_device(a, b, name);
+    on_device_of(a, rest...);
+}
 // [B, N] spins against the graph: -> B
 inline int64_t env_rows(const Tensor& t, const char* name, const rls_graph* g) {
     TORCH_CHECK(t.dim() == 2 && t.size(1) == g->num_nodes, name, " must be [B, ", g->num_nodes, "], got ", t.sizes());
@@ -100,6 +112,7 @@ void maxcut_obj(int64_t g, const Tensor& xs, Tensor obj) {
     const int64_t B = env_rows(xs, "xs", G(g));
     dev(obj, "obj", I64);
     count(obj, "obj", B);
+    on_device_of(xs, "obj", obj);
     RLS_GUARD(xs);
     ok(rls_maxcut_obj(G(g), p(xs), sb, B, (int64_t*)p(obj), cur_stream(xs)), "rls_maxcut_obj");
 }
@@ -108,6 +121,7 @@ void maxcut_edge_cut_mask(int64_t g, const Tensor& xs, Tensor mask) {
     const int64_t B = env_rows(xs, "xs", G(g));
     spin_bytes(mask, "mask", false);
     shape2(mask, "mask", B, G(g)->num_stored_edges);
+    on_device_of(xs, "mask", mask);
     RLS_GUARD(xs);
     ok(rls_maxcut_edge_cut_mask(G(g), (const uint8_t*)p(xs), B, (uint8_t*)p(mask), cur_stream(xs)), "rls_maxcut_edge_cut_mask");
 }
@@ -116,6 +130,7 @@ void maxcut_node_cutdeg(int64_t g, const Tensor& xs, Tensor out) {
     const int64_t B = env_rows(xs, "xs", G(g));
     dev(out, "out", I64);
     shape2(out, "out", B, G(g)->num_nodes);
+    on_device_of(xs, "out", out);
     RLS_GUARD(xs);
     ok(rls_maxcut_node_cutdeg(G(g), (const uint8_t*)p(xs), B, (int64_t*)p(out), cur_stream(xs)), "rls_maxcut_node_cutdeg");
 }
@@ -124,6 +139,7 @@ void maxcut_delta_all(int64_t g, const Tensor& xs, Tensor out) {
     const int64_t B = env_rows(xs, "xs", G(g));
     dev(out, "out", I32);
     shape2(out, "out", B, G(g)->num_nodes);
+    on_device_of(xs, "out", out);
     RLS_GUARD(xs);
     ok(rls_maxcut_delta_all(G(g), (const uint8_t*)p(xs), B, (int32_t*)p(out), cur_stream(xs)), "rls_maxcut_delta_all");
 }
@@ -142,6 +158,7 @@ void maxcut_step(int64_t g, const Tensor& x_in, Tensor x_out, const Tensor& acti
     count(reward, "reward", B);
     if (cur.has_value()) count(*cur, "cur", B);
     if (done.has_value()) count(*done, "done", B);
+    on_device_of(x_in, "x_out", x_out, "action", action, "obj", obj, "reward", reward, "cur", cur, "done", done);
     RLS_GUARD(x_in);
     ok(rls_maxcut_step(G(g), p(x_in), p(x_out), sb, B, (const int64_t*)p(action), (int32_t*)p(obj), (float*)p(reward),
                        (float*)p(cur), (float*)p(done), (float)done_value, cur_stream(x_in)), "rls_maxcut_step");
@@ -151,6 +168,7 @@ void maxcut_greedy_sweep(int64_t g, Tensor xs, Tensor obj) {
     const int64_t B = env_rows(xs, "xs", G(g));
     dev(obj, "obj", I64);
     count(obj, "obj", B);
+    on_device_of(xs, "obj", obj);
     RLS_GUARD(xs);
     ok(rls_maxcut_greedy_sweep(G(g), (uint8_t*)p(xs), B, (int64_t*)p(obj), cur_stream(xs)), "rls_maxcut_greedy_sweep");
 }
@@ -167,6 +185,7 @@ void maxcut_propose_accept(int64_t g, Tensor xs, const Tensor& mask, Tensor obj)
     }
     dev(obj, "obj", I64);
     count(obj, "obj", B);
+    on_device_of(xs, "mask", mask, "obj", obj);
     RLS_GUARD(xs);
     ok(rls_maxcut_propose_accept(G(g), (uint8_t*)p(xs), B, p(mask), packed ? 1 : 0, (int64_t*)p(obj), cur_stream(xs)),
        "rls_maxcut_propose_accept");
@@ -188,6 +207,7 @@ void maxcut_ls_weights(int64_t g, const Tensor& xs, int64_t mult, Tensor ws, con
                 ws.sizes());
     optdev(ws_minmax, "ws_minmax", I32);
     if (ws_minmax.has_value()) shape2(*ws_minmax, "ws_minmax", 2, G(g)->num_nodes);
+    on_device_of(xs, "ws", ws, "ws_minmax", ws_minmax);
     RLS_GUARD(xs);
     ok(rls_maxcut_ls_weights(G(g), (const uint8_t*)p(xs), B, (int32_t)mult, p(ws), wb, ws.size(1), (int32_t*)p(ws_minmax), cur_stream(xs)),
        "rls_maxcut_ls_weights");
@@ -207,6 +227,7 @@ void maxcut_local_search(int64_t g, Tensor xs, const Tensor& ws, const Tensor& r
                     "noise must be [>= num_iters + 1 - first_draw_proposes, B, N], got ", noise->sizes());
     dev(obj, "obj", I64);
     count(obj, "obj", B);
+    on_device_of(xs, "ws", ws, "rd_std", rd_std, "noise", noise, "obj", obj);
     RLS_GUARD(xs);
     ok(rls_maxcut_local_search(G(g), (uint8_t*)p(xs), B, p(ws), wb, ws.size(1), (const float*)p(rd_std), (const float*)p(noise),
                                (uint64_t)seed, env_offset, (int32_t)num_iters, (int32_t)num_spin, first_draw_proposes, (int64_t*)p(obj),
@@ -234,6 +255,7 @@ void maxcut_ls_threshold(int64_t g, const Tensor& ws, const Tensor& rd_std, int6
     count(rd_std, "rd_std", N);
     dev(thresh, "thresh", F32);
     count(thresh, "thresh", B);
+    on_device_of(ws, "rd_std", rd_std, "thresh", thresh, "scratch", scratch);
     RLS_GUARD(ws);
     ok(rls_maxcut_ls_threshold(G(g), B, p(ws), wb, ws.size(1), (const float*)p(rd_std), (uint64_t)seed, env_offset, (int32_t)draw, (int32_t)num_spin,
                                (float*)p(thresh), p(scratch), scratch_of(scratch), cur_stream(ws)), "rls_maxcut_ls_threshold");
@@ -250,6 +272,7 @@ void maxcut_ls_propose(int64_t g, Tensor xs, const Tensor& ws, const Tensor& rd_
     count(thresh, "thresh", B);
     dev(obj, "obj", I64);
     count(obj, "obj", B);
+    on_device_of(xs, "ws", ws, "rd_std", rd_std, "thresh", thresh, "obj", obj, "scratch", scratch);
     RLS_GUARD(xs);
     ok(rls_maxcut_ls_propose(G(g), (uint8_t*)p(xs), B, p(ws), wb, ws.size(1), (const float*)p(rd_std), (const float*)p(thresh), (uint64_t)seed,
                              env_offset, (int32_t)draw, (int64_t*)p(obj), p(scratch), scratch_of(scratch), cur_stream(xs)),
@@ -267,6 +290,7 @@ void maxcut_ls_rounds(int64_t g, Tensor xs, const Tensor& ws, const Tensor& rd_s
     count(thresh, "thresh", B);
     dev(obj, "obj", I64);
     count(obj, "obj", B);
+    on_device_of(xs, "ws", ws, "rd_std", rd_std, "thresh", thresh, "obj", obj, "scratch", scratch);
     RLS_GUARD(xs);
     ok(rls_maxcut_ls_rounds(G(g), (uint8_t*)p(xs), B, p(ws), wb, ws.size(1), (const float*)p(rd_std), (const float*)p(thresh), (uint64_t)seed,
                             env_offset, (int32_t)first_draw, (int32_t)num_draws, (int64_t*)p(obj), p(scratch), scratch_of(scratch), cur_stream(xs)),
@@ -280,6 +304,7 @@ void select_better_rows(Tensor xs0, Tensor vs0, const Tensor& xs1, const Tensor&
     dev(vs1, "vs1", I64);
     count(vs0, "vs0", xs0.size(0));
     count(vs1, "vs1", xs0.size(0));
+    on_device_of(xs0, "vs0", vs0, "xs1", xs1, "vs1", vs1);
     RLS_GUARD(xs0);
     ok(rls_select_better_rows((uint8_t*)p(xs0), (int64_t*)p(vs0), (const uint8_t*)p(xs1), (const int64_t*)p(vs1), xs0.size(0), xs0.size(1),
                               if_maximize, cur_stream(xs0)), "rls_select_better_rows");
@@ -294,22 +319,26 @@ void pick_best_of_repeats(const Tensor& xs, const Tensor& vs, int64_t R, bool if
     count(vs, "vs", xs.size(0));
     shape2(good_xs, "good_xs", S, xs.size(1));
     count(good_vs, "good_vs", S);
+    on_device_of(xs, "vs", vs, "good_xs", good_xs, "good_vs", good_vs);
     RLS_GUARD(xs);
     ok(rls_pick_best_of_repeats((const uint8_t*)p(xs), (const int64_t*)p(vs), R, S, xs.size(1), if_maximize, (uint8_t*)p(good_xs),
                                 (int64_t*)p(good_vs), cur_stream(xs)), "rls_pick_best_of_repeats");
 }
-void copy_rows(Tensor xs, const OptTensor& vs, const Tensor& dst, const Tensor& src) {
+// both ops know B from xs and hand it to the kernel: a dst / src outside [0, B) is a skipped move (rlsolver_hip.h: rls_copy_rows_bounded)
+void copy_rows_bounded(Tensor xs, const OptTensor& vs, const Tensor& dst, const Tensor& src) {
     spin_bytes(xs, "xs", false);
-    TORCH_CHECK(xs.dim() == 2, "xs must be [B, N]");
+    TORCH_CHECK(xs.dim() == 2 && xs.size(1) >= 1, "xs must be [B, N] with N >= 1, got ", xs.sizes());
     optdev(vs, "vs", I64);
     if (vs.has_value()) count(*vs, "vs", xs.size(0));
     dev(dst, "dst", I64);
     dev(src, "src", I64);
     count(src, "src", dst.numel());
+    on_device_of(xs, "vs", vs, "dst", dst, "src", src);
     RLS_GUARD(xs);
-    ok(rls_copy_rows((uint8_t*)p(xs), (int64_t*)p(vs), xs.size(1), (const int64_t*)p(dst), (const int64_t*)p(src), dst.numel(), cur_stream(xs)),
-       "rls_copy_rows");
+    ok(rls_copy_rows_bounded((uint8_t*)p(xs), (int64_t*)p(vs), xs.size(0), xs.size(1), (const int64_t*)p(dst), (const int64_t*)p(src), dst.numel(),
+                             cur_stream(xs)), "rls_copy_rows_bounded");
 }
+void copy_rows(Tensor xs, const OptTensor& vs, const Tensor& dst, const Tensor& src) { copy_rows_bounded(xs, vs, dst, src); }
 void best_update(const Tensor& xs, const Tensor& vs, bool if_maximize, Tensor best_x, Tensor best_v, Tensor improved, const OptTensor& log_v,
                  int64_t log_index, bool force) {
     spin_bytes(xs, "xs", false);
@@ -325,6 +354,7 @@ void best_update(const Tensor& xs, const Tensor& vs, bool if_maximize, Tensor be
     count(best_v, "best_v", 1);
     count(improved, "improved", 1);
     if (log_v.has_value()) TORCH_CHECK(log_index >= 0 && log_index < log_v->numel(), "log_index outside log_v");
+    on_device_of(xs, "vs", vs, "best_x", best_x, "best_v", best_v, "improved", improved, "log_v", log_v);
     RLS_GUARD(xs);
     ok(rls_best_update((const uint8_t*)p(xs), p(vs), kind, vs.numel(), best_x.numel(), if_maximize, (uint8_t*)p(best_x), (double*)p(best_v),
                        (uint8_t*)p(improved), (double*)p(log_v), log_index, force, cur_stream(xs)), "rls_best_update");
@@ -341,6 +371,7 @@ void best_key(const Tensor& vs, int64_t rank_bits, int64_t low_code, int64_t lim
     at_least(key, "key", 1);
     at_least(flag, "flag", 1);
     if (index.has_value()) at_least(*index, "index", 1);
+    on_device_of(vs, "key", key, "index", index, "flag", flag);
     RLS_GUARD(vs);
     ok(rls_best_key(p(vs), kind, vs.numel(), (int32_t)rank_bits, low_code, limit, (int64_t*)p(key), (int64_t*)p(index), (int32_t*)p(flag),
                     cur_stream(vs)), "rls_best_key");
@@ -356,7 +387,7 @@ void key_unpack(const Tensor& key, int64_t rank_bits, int64_t world, Tensor obj,
     optdev(flag, "flag", I32);
     if (owner.has_value()) at_least(*owner, "owner", 1);
     if (flag.has_value()) at_least(*flag, "flag", 1);
-    same_device(key, obj, "obj");
+    on_device_of(key, "obj", obj, "owner", owner, "flag", flag);
     RLS_GUARD(key);
     ok(rls_key_unpack((const int64_t*)p(key), (int32_t)rank_bits, world, obj.scalar_type() == F64, p(obj), (int64_t*)p(owner), empty_key,
                       (int32_t*)p(flag), cur_stream(key)), "rls_key_unpack");
@@ -373,11 +404,10 @@ void winner_message(const OptTensor& xs, const OptTensor& index, const Tensor& k
         spin_bytes(*xs, "xs", false);
         TORCH_CHECK((xs->dim() == 2 && xs->size(1) == N) || (xs->dim() == 1 && xs->size(0) == N), "xs must be [B, N] or [N]");
         B = xs->dim() == 2 ? xs->size(0) : 1;
-        same_device(key, *xs, "xs");
         TORCH_CHECK(B <= 1 || index.has_value(), "a [B, N] xs needs the row index");
     }
     if (index.has_value()) at_least(*index, "index", 1);
-    same_device(key, msg, "msg");
+    on_device_of(key, "xs", xs, "index", index, "msg", msg);
     RLS_GUARD(key);
     ok(rls_winner_message((const uint8_t*)p(xs), B, N, (const int64_t*)p(index), (const int64_t*)p(key), (int32_t)rank_bits, my_low_code,
                           env_offset, (uint8_t*)p(msg), cur_stream(key)), "rls_winner_message");
@@ -385,9 +415,10 @@ void winner_message(const OptTensor& xs, const OptTensor& index, const Tensor& k
 void winner_unpack(const Tensor& msg, int64_t N, const OptTensor& x_out, const OptTensor& index_out) {
     dev(msg, "msg", at::kByte);
     TORCH_CHECK(msg.is_contiguous() && msg.numel() == 8 + (N + 7) / 8, "msg must hold 8 + ceil(N / 8) bytes");
-    if (x_out.has_value()) { spin_bytes(*x_out, "x_out", false); TORCH_CHECK(x_out->numel() == N && x_out->is_contiguous(), "x_out must be [N]"); same_device(msg, *x_out, "x_out"); }
+    if (x_out.has_value()) { spin_bytes(*x_out, "x_out", false); TORCH_CHECK(x_out->numel() == N && x_out->is_contiguous(), "x_out must be [N]"); }
     optdev(index_out, "index_out", I64);
     if (index_out.has_value()) at_least(*index_out, "index_out", 1);
+    on_device_of(msg, "x_out", x_out, "index_out", index_out);
     RLS_GUARD(msg);
     ok(rls_winner_unpack((const uint8_t*)p(msg), N, (uint8_t*)p(x_out), (int64_t*)p(index_out), cur_stream(msg)), "rls_winner_unpack");
 }
@@ -400,8 +431,8 @@ void rand_spins(Tensor x, int64_t seed, int64_t env_offset) {
 void rand_spins_repeats(Tensor x, Tensor repeat_seeds, int64_t env_offset) {
     spin_bytes(x, "x", false);
     dev(repeat_seeds, "repeat_seeds", I64);
-    same_device(x, repeat_seeds, "repeat_seeds");
     TORCH_CHECK(x.dim() == 3 && repeat_seeds.dim() == 1 && repeat_seeds.size(0) == x.size(0), "x must be [R, S, N] and repeat_seeds [R]");
+    on_device_of(x, "repeat_seeds", repeat_seeds);
     RLS_GUARD(x);
     ok(rls_rand_spins_repeats((uint8_t*)p(x), x.size(0), x.size(1), x.size(2), (const uint64_t*)p(repeat_seeds), env_offset, cur_stream(x)),
        "rls_rand_spins_repeats");
@@ -425,12 +456,10 @@ void sub_set_sampling(const Tensor& probs, const Tensor& start_xs, int64_t R, in
     TORCH_CHECK(env_offset >= 0, "env_offset must be >= 0, got ", env_offset);
     TORCH_CHECK(S == 0 || R <= INT64_MAX / N / S, "R * S * N = ", R, " * ", S, " * ", N, " does not fit int64");
     shape2(xs_out, "xs_out", R * S, N);
-    same_device(probs, start_xs, "start_xs");
-    same_device(probs, xs_out, "xs_out");
     optdev(uniforms, "uniforms", F32);
-    if (uniforms.has_value()) { shape2(*uniforms, "uniforms", R * S, N); same_device(probs, *uniforms, "uniforms"); }
+    if (uniforms.has_value()) shape2(*uniforms, "uniforms", R * S, N);
     optdev(probs_out, "probs_out", F32);
-    if (probs_out.has_value()) { shape2(*probs_out, "probs_out", S, N); same_device(probs, *probs_out, "probs_out"); }
+    if (probs_out.has_value()) shape2(*probs_out, "probs_out", S, N);
     // workgroups re-read the inputs while others write the outputs: shared bytes would be a race, not an in-place form
     TORCH_CHECK(!overlaps(xs_out, start_xs), "xs_out overlaps start_xs");
     TORCH_CHECK(!overlaps(xs_out, probs), "xs_out overlaps probs");
@@ -440,6 +469,7 @@ void sub_set_sampling(const Tensor& probs, const Tensor& start_xs, int64_t R, in
                     "probs_out overlaps another argument");
         if (uniforms.has_value()) TORCH_CHECK(!overlaps(*probs_out, *uniforms), "probs_out overlaps uniforms");
     }
+    on_device_of(probs, "start_xs", start_xs, "uniforms", uniforms, "xs_out", xs_out, "probs_out", probs_out);
     RLS_GUARD(probs);
     ok(rls_sub_set_sampling((const float*)p(probs), (const uint8_t*)p(start_xs), S, N, R, top_k, (const float*)p(uniforms), (uint64_t)seed,
                             env_offset, (uint8_t*)p(xs_out), (float*)p(probs_out), cur_stream(probs)), "rls_sub_set_sampling");
@@ -476,9 +506,6 @@ rls_s2vppo_env s2v_env(const Tensor& ptr, const Tensor& rowptr, const Tensor& co
     dev(basins, "basins", I64); count(basins, "basins", multiplier * T);
     dev(x, "x", F32); shape2(x, "x", T, 5);
     spin_bytes(mask, "mask", false); count(mask, "mask", T);
-    const Tensor* all[] = {&rowptr, &col, &w, &wtot, &z, &delta, &last_flip, &best_z, &counters, &cut, &best_cut, &tabu, &hash, &basins, &x, &mask};
-    const char* names[] = {"rowptr", "col", "w", "wtot", "z", "delta", "last_flip", "best_z", "counters", "cut", "best_cut", "tabu", "hash", "basins", "x", "mask"};
-    for (int i = 0; i < 16; ++i) same_device(ptr, *all[i], names[i]);
     rls_s2vppo_env e{};
     e.num_envs = B; e.total_nodes = T; e.max_nodes = max_nodes; e.nnz = col.numel(); e.tenure = tenure; e.multiplier = multiplier;
     e.ptr = (const int64_t*)p(ptr); e.rowptr = (const int64_t*)p(rowptr); e.col = (const int32_t*)p(col); e.w = (const float*)p(w);
@@ -493,9 +520,12 @@ void s2vppo_step(const Tensor& ptr, const Tensor& rowptr, const Tensor& col, con
                  Tensor done) {
     const rls_s2vppo_env e = s2v_env(ptr, rowptr, col, w, wtot, z, delta, last_flip, best_z, counters, cut, best_cut, tabu, hash, basins, x, mask,
                                      max_nodes, tenure, multiplier);
-    dev(action, "action", I64); count(action, "action", e.num_envs); same_device(ptr, action, "action");
-    dev(reward, "reward", F64); count(reward, "reward", e.num_envs); same_device(ptr, reward, "reward");
-    spin_bytes(done, "done", false); count(done, "done", e.num_envs); same_device(ptr, done, "done");
+    dev(action, "action", I64); count(action, "action", e.num_envs);
+    dev(reward, "reward", F64); count(reward, "reward", e.num_envs);
+    spin_bytes(done, "done", false); count(done, "done", e.num_envs);
+    on_device_of(ptr, "rowptr", rowptr, "col", col, "w", w, "wtot", wtot, "z", z, "delta", delta, "last_flip", last_flip, "best_z", best_z,
+                 "counters", counters, "cut", cut, "best_cut", best_cut, "tabu", tabu, "hash", hash, "basins", basins, "x", x, "mask", mask,
+                 "action", action, "reward", reward, "done", done);
     RLS_GUARD(ptr);
     ok(rls_s2vppo_step(&e, (const int64_t*)p(action), stag_punishment, (double*)p(reward), (uint8_t*)p(done), cur_stream(ptr)), "rls_s2vppo_step");
 }
@@ -506,11 +536,14 @@ void s2vppo_reset(const Tensor& ptr, const Tensor& rowptr, const Tensor& col, co
     const rls_s2vppo_env e = s2v_env(ptr, rowptr, col, w, wtot, z, delta, last_flip, best_z, counters, cut, best_cut, tabu, hash, basins, x, mask,
                                      max_nodes, tenure, multiplier);
     optdev(ids, "ids", I64);
-    if (ids.has_value()) { TORCH_CHECK(ids->dim() == 1, "ids must be one-dimensional, got ", ids->sizes()); same_device(ptr, *ids, "ids"); }
+    if (ids.has_value()) TORCH_CHECK(ids->dim() == 1, "ids must be one-dimensional, got ", ids->sizes());
     optdev(z0, "z0", at::kChar);
-    if (z0.has_value()) { count(*z0, "z0", e.total_nodes); same_device(ptr, *z0, "z0"); }
-    if (greedy.has_value()) { spin_bytes(*greedy, "greedy", false); count(*greedy, "greedy", e.num_envs); same_device(ptr, *greedy, "greedy"); }
+    if (z0.has_value()) count(*z0, "z0", e.total_nodes);
+    if (greedy.has_value()) { spin_bytes(*greedy, "greedy", false); count(*greedy, "greedy", e.num_envs); }
     TORCH_CHECK(env_offset >= 0, "env_offset must be >= 0, got ", env_offset);
+    on_device_of(ptr, "rowptr", rowptr, "col", col, "w", w, "wtot", wtot, "z", z, "delta", delta, "last_flip", last_flip, "best_z", best_z,
+                 "counters", counters, "cut", cut, "best_cut", best_cut, "tabu", tabu, "hash", hash, "basins", basins, "x", x, "mask", mask,
+                 "ids", ids, "z0", z0, "greedy", greedy);
     RLS_GUARD(ptr);
     ok(rls_s2vppo_reset(&e, (const int64_t*)p(ids), ids.has_value() ? ids->numel() : e.num_envs, (const int8_t*)p(z0), (const uint8_t*)p(greedy),
                         (uint64_t)seed, env_offset, cur_stream(ptr)), "rls_s2vppo_reset");
@@ -567,6 +600,7 @@ void spin_observation(int64_t env, const Tensor& state, const Tensor& row_index,
         TORCH_CHECK((matrix->dim() == 2 || (per_env && matrix->size(0) == B)) && matrix->size(-2) == N && matrix->size(-1) == N,
                     "matrix must be [N, N] or [B, N, N]");
     }
+    on_device_of(state, "matrix", matrix, "out", out);
     RLS_GUARD(state);
     ok(rls_spin_observation(SE(env), p(matrix), per_env, sb, B, (int32_t)R, N, (const int32_t*)p(row_index), step_index, binary_basis, p(out),
                             cur_stream(state)), "rls_spin_observation");
@@ -598,6 +632,7 @@ void spin_reset_dense(const Tensor& matrix, int64_t env, const Tensor& state, co
     const int64_t B = state.size(0), N = state.size(2);
     shape3(matrix, "matrix", B, N, N);
     TORCH_CHECK(max_local.numel() == B && weight_sum.numel() == B && flags.numel() == B, "max_local / weight_sum / flags must hold B entries");
+    on_device_of(state, "matrix", matrix, "max_local", max_local, "weight_sum", weight_sum, "flags", flags);
     RLS_GUARD(state);
     ok(rls_spin_reset_dense(p(matrix), SE(env), sb, B, N, (int32_t)state.size(1), (const int32_t*)p(row_index),
                             p(max_local), p(weight_sum), (uint8_t*)p(flags), cur_stream(state)), "rls_spin_reset_dense");
@@ -617,6 +652,7 @@ void spin_step_dense(const Tensor& matrix, const Tensor& max_local, int64_t env,
     TORCH_CHECK(max_local.numel() == B && action.numel() == B && reward.numel() == B, "max_local / action / reward must hold B entries");
     if (visited_new.has_value()) count(*visited_new, "visited_new", B);
     TORCH_CHECK(hist_len >= 0 && (SE(env)->hist == nullptr || hist_len <= SE(env)->hist_cap), "hist_len outside the visited-state ring");
+    on_device_of(state, "matrix", matrix, "max_local", max_local, "action", action, "reward", reward, "visited_new", visited_new);
     RLS_GUARD(state);
     ok(rls_spin_step_dense(p(matrix), p(max_local), SE(env), sb, B, N, (int32_t)state.size(1),
                            (const int32_t*)p(row_index), (const int64_t*)p(action), p(reward), (uint8_t*)p(visited_new), termination_value,
@@ -636,6 +672,7 @@ void spin_step(int64_t g, int64_t env, const Tensor& state, const Tensor& row_in
     TORCH_CHECK(action.numel() == B && reward.numel() == B, "action / reward must hold B entries");
     if (visited_new.has_value()) count(*visited_new, "visited_new", B);
     TORCH_CHECK(hist_len >= 0 && (SE(env)->hist == nullptr || hist_len <= SE(env)->hist_cap), "hist_len outside the visited-state ring");
+    on_device_of(state, "action", action, "reward", reward, "visited_new", visited_new);
     RLS_GUARD(state);
     ok(rls_spin_step(G(g), SE(env), sb, B, (int32_t)state.size(1), (const int32_t*)p(row_index),
                      (const int64_t*)p(action), p(reward), (uint8_t*)p(visited_new), max_local, termination_value, (int32_t)reward_mode,
@@ -682,6 +719,7 @@ void mcpg_metro_rounds(Tensor samples, const OptTensor& samples_in, int64_t C_in
         TORCH_CHECK(u->dim() == 2 && u->size(0) >= t_offset + T && u->size(1) == C, "u must be [>= t_offset + T, C]");
     }
     optdev(t_limit, "t_limit", I64);
+    if (t_limit.has_value()) at_least(*t_limit, "t_limit", 1);      // the kernel reads t_limit[0]
     optdev(accepts, "accepts", I64);
     int64_t accept_rows = 1;      // accepts is [T] or [rows, T]
     if (accepts.has_value()) {
@@ -691,10 +729,11 @@ void mcpg_metro_rounds(Tensor samples, const OptTensor& samples_in, int64_t C_in
     int64_t scratch_bytes = 0;
     if (scratch.has_value()) {
         dev(*scratch, "scratch");
-        same_device(samples, *scratch, "scratch");
         TORCH_CHECK(scratch->is_contiguous(), "scratch must be contiguous");
         scratch_bytes = (int64_t)scratch->nbytes();
     }
+    on_device_of(samples, "samples_in", samples_in, "probs", probs, "index", index, "u", u, "t_limit", t_limit, "accepts", accepts,
+                 "scratch", scratch);
     RLS_GUARD(samples);
     ok(rls_mcpg_metro_rounds(p(samples), p(samples_in), C_in, sb, N, C, (const float*)p(probs), T, t_offset, (const int64_t*)p(index),
                              (const float*)p(u), (uint64_t)seed, (const int64_t*)p(t_limit), write_back, (int64_t*)p(accepts), accept_rows,
@@ -708,6 +747,7 @@ void mcpg_metro_stop(const Tensor& accepts, int64_t target, int64_t first, int64
     count(ctl, "ctl", 3);
     optdev(apply_limit, "apply_limit", I64);
     if (apply_limit.has_value()) count(*apply_limit, "apply_limit", 1);
+    on_device_of(accepts, "ctl", ctl, "apply_limit", apply_limit);
     RLS_GUARD(accepts);
     TORCH_CHECK(first >= 0 && first <= 2, "first must be 0, 1 or 2");
     ok(rls_mcpg_metro_stop((const int64_t*)p(accepts), accepts.size(0), accepts.size(1), target, (int32_t)first, next_T, (int64_t*)p(ctl),
@@ -734,6 +774,8 @@ void mcpg_local_search(int64_t g, const Tensor& xs_in, Tensor xs_out, const Tens
     TORCH_CHECK(gauge_node >= -1 && gauge_node < N, "gauge_node outside [-1, N)");
     dev(expected, "expected", F32);
     count(expected, "expected", C);
+    on_device_of(xs_in, "xs_out", xs_out, "order", order, "visit_stream", visit_stream, "uniforms", uniforms, "edge_weights", edge_weights,
+                 "expected", expected);
     RLS_GUARD(xs_in);
     ok(rls_mcpg_local_search(G(g), p(xs_in), sb, (float*)p(xs_out), C, (const int32_t*)p(order), (const int32_t*)p(visit_stream),
                              visit_stream.has_value() ? visit_stream->numel() : 0, num_ls, (const float*)p(uniforms), (uint64_t)seed,
@@ -755,6 +797,7 @@ void mcpg_local_search_levels(int64_t g, const Tensor& xs_in, int64_t C_in, Tens
     if (coins.has_value()) shape2(*coins, "coins", num_ls * N, (C + 63) / 64);
     dev(expected, "expected", F32);
     count(expected, "expected", C);
+    on_device_of(xs_in, "xs_out", xs_out, "lv_ptr", lv_ptr, "lv_data", lv_data, "coins", coins, "expected", expected);
     RLS_GUARD(xs_in);
     ok(rls_mcpg_local_search_levels(G(g), p(xs_in), sb, C_in, p(xs_out), osb, C, (const int32_t*)p(lv_ptr), (const int32_t*)p(lv_data),
                                     lv_ptr.numel() - 1, num_ls, (const uint64_t*)p(coins), (uint64_t)seed, (float*)p(expected), cid.ptr(), cur_stream(xs_in)),
@@ -771,7 +814,6 @@ void maxsat_local_search(const Tensor& xs_in, int64_t C_in, Tensor xs_out, int64
     const int osb = chain_bytes(xs_out, "xs_out");
     TORCH_CHECK(osb == 0 || osb == 4, "xs_out must be float32 node-major or bit-packed");
     chain_shape(xs_out, osb, nvar, C, "xs_out");
-    same_device(xs_in, xs_out, "xs_out");
     dev(lv_ptr, "lv_ptr", I32);
     dev(lv_data, "lv_data", I32);
     TORCH_CHECK(lv_ptr.numel() >= 2, "lv_ptr must hold groups + 1 offsets");
@@ -787,7 +829,8 @@ void maxsat_local_search(const Tensor& xs_in, int64_t C_in, Tensor xs_out, int64
     if (weight.has_value()) count(*weight, "weight", M);
     dev(expected, "expected", F32);
     count(expected, "expected", C);
-    for (const Tensor* t : {&lv_ptr, &lv_data, &clause_ptr, &lit, (const Tensor*)&expected}) same_device(xs_in, *t, "every tensor");
+    on_device_of(xs_in, "xs_out", xs_out, "lv_ptr", lv_ptr, "lv_data", lv_data, "coins", coins, "clause_ptr", clause_ptr, "lit", lit,
+                 "weight", weight, "expected", expected);
     RLS_GUARD(xs_in);
     ok(rls_maxsat_local_search(p(xs_in), C_in, p(xs_out), osb, C, nvar, (const int32_t*)p(lv_ptr), (const int32_t*)p(lv_data), lv_ptr.numel() - 1,
                                num_ls, (const uint64_t*)p(coins), (uint64_t)seed, (const int32_t*)p(clause_ptr), (const int32_t*)p(lit),
@@ -814,9 +857,7 @@ void cheeger_local_search(int64_t g, const Tensor& xs_in, int64_t C_in, Tensor x
     if (cut.has_value()) count(*cut, "cut", C);
     optdev(size, "size", F32);
     if (size.has_value()) count(*size, "size", C);
-    for (const Tensor* t : {(const Tensor*)&xs_out, &visit_stream, (const Tensor*)&h}) same_device(xs_in, *t, "every tensor");
-    if (cut.has_value()) same_device(xs_in, *cut, "cut");
-    if (size.has_value()) same_device(xs_in, *size, "size");
+    on_device_of(xs_in, "xs_out", xs_out, "visit_stream", visit_stream, "h", h, "cut", cut, "size", size);
     RLS_GUARD(xs_in);
     ok(rls_cheeger_local_search(G(g), p(xs_in), C_in, p(xs_out), osb, C, (const int32_t*)p(visit_stream), visit_stream.numel(), (int)normalized, num_ls,
                                 (float)edge_weight_sum, (float*)p(h), (float*)p(cut), (float*)p(size), cur_stream(xs_in)),
@@ -848,8 +889,7 @@ void maxcut_edge_local_search(int64_t g, const Tensor& edge_weights, const Tenso
                     "uniforms must be [num_ls, E, 3, C] = [", num_ls, ", ", E, ", 3, ", C, "], got ", uniforms->sizes());
     dev(expected, "expected", F32);
     count(expected, "expected", C);
-    for (const Tensor* t : {(const Tensor*)&xs_out, &edge_weights, &visit_stream, (const Tensor*)&expected}) same_device(xs_in, *t, "every tensor");
-    if (uniforms.has_value()) same_device(xs_in, *uniforms, "uniforms");
+    on_device_of(xs_in, "edge_weights", edge_weights, "xs_out", xs_out, "visit_stream", visit_stream, "uniforms", uniforms, "expected", expected);
     RLS_GUARD(xs_in);
     ok(rls_maxcut_edge_local_search(G(g), (const int32_t*)p(edge_weights), p(xs_in), C_in, p(xs_out), osb, C, (const int32_t*)p(visit_stream),
                                     visit_stream.numel(), max_abs_degree, weight_abs_sum, (int)gauge_node, num_ls, (const float*)p(uniforms),
@@ -869,12 +909,11 @@ void mimo_local_search(const Tensor& Sigma, const Tensor& Diag, const Tensor& xs
     optdev(xs_out, "xs_out", I64);
     if (xs_out.has_value()) {
         chain_shape(*xs_out, 0, n, C, "xs_out");
-        same_device(Sigma, *xs_out, "xs_out");
         TORCH_CHECK(num_ls >= 1, "num_ls must be >= 1 (a sweep-less call would leave +-2 entries), got ", num_ls);
     }
     dev(expected, "expected", F32);
     count(expected, "expected", C);
-    for (const Tensor* t : {&Diag, &xs_in, (const Tensor*)&expected}) same_device(Sigma, *t, "every tensor");
+    on_device_of(Sigma, "Diag", Diag, "xs_in", xs_in, "xs_out", xs_out, "expected", expected);
     RLS_GUARD(Sigma);
     ok(rls_mimo_local_search((const float*)p(Sigma), (const float*)p(Diag), n, (const uint64_t*)p(xs_in), C_in, (uint64_t*)p(xs_out), C, num_ls,
                              (float*)p(expected), cur_stream(Sigma)), "rls_mimo_local_search");
@@ -892,6 +931,7 @@ void mcpg_pick_best(const Tensor& expected, const Tensor& xs, int64_t N, int64_t
     dev(vs_good, "vs_good", F32);
     count(best_index, "best_index", total_mcmc_num);
     count(vs_good, "vs_good", total_mcmc_num);
+    on_device_of(xs, "expected", expected, "best_index", best_index, "vs_good", vs_good, "xs_good", xs_good);
     RLS_GUARD(xs);
     ok(rls_mcpg_pick_best((const float*)p(expected), p(xs), sb, N, total_mcmc_num, repeat_times, num_edges, (int64_t*)p(best_index),
                           (float*)p(vs_good), p(xs_good), cur_stream(xs)), "rls_mcpg_pick_best");
@@ -914,6 +954,8 @@ void mcpg_merge_best(const Tensor& temp_max, Tensor temp_info, Tensor now_max_re
     if (best_value.has_value()) at_least(*best_value, "best_value", replace_worst ? 1 : 2);
     if (best_index.has_value()) at_least(*best_index, "best_index", replace_worst ? 1 : 2);
     TORCH_CHECK(replace_worst || (best_value.has_value() && best_index.has_value()), "replace_worst = False reports {max, min} in best_value / best_index [2]");
+    on_device_of(temp_info, "temp_max", temp_max, "now_max_res", now_max_res, "now_info", now_info, "mask_scratch", mask_scratch,
+                 "best_value", best_value, "best_index", best_index);
     RLS_GUARD(temp_info);
     ok(rls_mcpg_merge_best((const float*)p(temp_max), (uint64_t*)p(temp_info), (float*)p(now_max_res), (uint64_t*)p(now_info), temp_info.size(1),
                            total_mcmc_num, (uint64_t*)p(mask_scratch), (float*)p(best_value), (int64_t*)p(best_index), replace_worst ? 1 : 0,
@@ -927,6 +969,7 @@ void mcpg_value_bit_sums(const Tensor& samples, int64_t C, const Tensor& value, 
     TORCH_CHECK(samples.dim() == 2 && samples.size(0) == (C + 63) / 64, "samples must be [ceil(C / 64), N]");
     count(value, "value", C);
     count(A, "A", samples.size(1));
+    on_device_of(samples, "value", value, "A", A);
     RLS_GUARD(samples);
     ok(rls_mcpg_value_bit_sums((const uint64_t*)p(samples), samples.size(1), C, (const float*)p(value), (float*)p(A), cur_stream(samples)),
        "rls_mcpg_value_bit_sums");
@@ -936,6 +979,7 @@ void mcpg_pack_chains(const Tensor& xs, Tensor packed) {
     TORCH_CHECK(sb != 0 && xs.dim() == 2, "xs must be node-major [N, C]");
     dev(packed, "packed", I64);
     shape2(packed, "packed", (xs.size(1) + 63) / 64, xs.size(0));
+    on_device_of(xs, "packed", packed);
     RLS_GUARD(xs);
     ok(rls_mcpg_pack_chains(p(xs), sb, xs.size(0), xs.size(1), (uint64_t*)p(packed), cur_stream(xs)), "rls_mcpg_pack_chains");
 }
@@ -944,6 +988,7 @@ void mcpg_unpack_chains(const Tensor& packed, int64_t C, Tensor xs) {
     dev(xs, "xs", F32);
     TORCH_CHECK(packed.dim() == 2 && packed.size(0) == (C + 63) / 64, "packed must be [ceil(C / 64), N]");
     shape2(xs, "xs", packed.size(1), C);
+    on_device_of(packed, "xs", xs);
     RLS_GUARD(packed);
     ok(rls_mcpg_unpack_chains((const uint64_t*)p(packed), packed.size(1), C, (float*)p(xs), cur_stream(packed)), "rls_mcpg_unpack_chains");
 }
@@ -956,6 +1001,7 @@ void qubo_local_search_value(const Tensor& Q, const Tensor& xs_in, Tensor xs_out
     TORCH_CHECK(xs_in.dim() == 2 && xs_in.size(0) == Q.size(0), "xs_in must be [n, C]");
     TORCH_CHECK(xs_out.sizes() == xs_in.sizes(), "xs_out must have the shape of xs_in");
     count(value, "value", xs_in.size(1));
+    on_device_of(Q, "xs_in", xs_in, "xs_out", xs_out, "value", value);
     RLS_GUARD(Q);
     ok(rls_qubo_local_search_value((const float*)p(Q), Q.size(0), (const float*)p(xs_in), (float*)p(xs_out), xs_in.size(1), num_ls, binary,
                                    (float*)p(value), cur_stream(Q)), "rls_qubo_local_search_value");
@@ -969,8 +1015,6 @@ void qubo_sparse_local_search_value(const Tensor& rowptr, const Tensor& col, con
     TORCH_CHECK(lv_ptr.has_value() == lv_rows.has_value(), "lv_ptr and lv_rows come together");
     if (lv_ptr.has_value()) {
         TORCH_CHECK(lv_ptr->numel() >= 2 && lv_rows->numel() == rowptr.numel() - 1, "lv_ptr must be [levels + 1], lv_rows [n]");
-        same_device(xs_in, *lv_ptr, "lv_ptr");
-        same_device(xs_in, *lv_rows, "lv_rows");
     }
     dev(col, "col", I32);
     dev(val, "val", F32);
@@ -981,6 +1025,7 @@ void qubo_sparse_local_search_value(const Tensor& rowptr, const Tensor& col, con
     TORCH_CHECK(col.numel() == val.numel(), "col and val must hold nnz entries each");
     TORCH_CHECK(xs_out.sizes() == xs_in.sizes(), "xs_out must have the shape of xs_in");
     count(value, "value", xs_in.size(1));
+    on_device_of(xs_in, "rowptr", rowptr, "col", col, "val", val, "lv_ptr", lv_ptr, "lv_rows", lv_rows, "xs_out", xs_out, "value", value);
     RLS_GUARD(xs_in);
     ok(rls_qubo_sparse_local_search_value((const int32_t*)p(rowptr), (const int32_t*)p(col), (const float*)p(val), rowptr.numel() - 1,
                                           (const int32_t*)p(lv_ptr), (const int32_t*)p(lv_rows),
@@ -999,6 +1044,7 @@ void tsp_tour_length(const Tensor& dist, const Tensor& perm, Tensor length) {
     perm_and_dist(dist, perm, F32);
     dev(length, "length", F32);
     count(length, "length", perm.size(0));
+    on_device_of(perm, "dist", dist, "length", length);
     RLS_GUARD(perm);
     ok(rls_tsp_tour_length((const float*)p(dist), perm.size(1), (const int64_t*)p(perm), perm.size(0), (float*)p(length), cur_stream(perm)),
        "rls_tsp_tour_length");
@@ -1024,18 +1070,17 @@ void tsp_swap_delta_all(const Tensor& dist, const Tensor& perm, const OptTensor&
     } else {
         TORCH_CHECK(nearest.has_value() && random.has_value(), "selected = None draws the partners in the kernel: nearest / random must be given");
         TORCH_CHECK(nearest->dim() == 2 && nearest->size(0) == N && random->dim() == 2 && random->size(0) == N, "nearest / random must be [N, *]");
-        same_device(perm, *nearest, "nearest");
-        same_device(perm, *random, "random");
         K = (int32_t)nearest->size(1);
         stride = (int32_t)random->size(1);
         if (selected_out.has_value()) TORCH_CHECK(selected_out->sizes() == perm.sizes(), "selected_out must have the shape of perm");
         if (tables8.has_value()) {
             dev(*tables8, "tables8", at::kByte);
-            same_device(perm, *tables8, "tables8");
             TORCH_CHECK(tables8->is_contiguous() && tables8->numel() == rls_tsp_tables8_bytes(N, K) && tables8->numel() > 0,
                         "tables8 must hold rls_tsp_tables8_bytes(N, K) bytes");
         }
     }
+    on_device_of(perm, "dist", dist, "selected", selected, "nearest", nearest, "random", random, "tables8", tables8, "selected_out", selected_out,
+                 "logratio", logratio, "indices", indices, "ban", ban);
     RLS_GUARD(perm);
     ok(rls_tsp_swap_delta_all((const float*)p(dist), N, (const int64_t*)p(perm), perm.size(0), (const int64_t*)p(selected),
                               (const int32_t*)p(nearest), K, (const int32_t*)p(random), stride, (const uint8_t*)p(tables8),
@@ -1050,6 +1095,7 @@ void tsp_apply_swap(Tensor perm, const Tensor& pos, const Tensor& indices) {
     dev(indices, "indices", I64);
     TORCH_CHECK(perm.dim() == 2 && indices.sizes() == perm.sizes(), "perm and indices must be [B, N]");
     count(pos, "pos", perm.size(0));
+    on_device_of(perm, "pos", pos, "indices", indices);
     RLS_GUARD(perm);
     ok(rls_tsp_apply_swap((int64_t*)p(perm), perm.size(0), perm.size(1), (const int64_t*)p(pos), (const int64_t*)p(indices), cur_stream(perm)),
        "rls_tsp_apply_swap");
@@ -1064,6 +1110,7 @@ void tsp_2opt_best(const Tensor& dist, const Tensor& perm, const OptTensor& cur_
     TORCH_CHECK(slices >= 1 && best_i.numel() == slices * perm.size(0) && best_j.numel() == best_i.numel() && best_value.numel() == best_i.numel(),
                 "outputs must hold slices * B entries each");
     if (cur_length.has_value()) TORCH_CHECK(cur_length->numel() == perm.size(0), "cur_length must hold B entries");
+    on_device_of(perm, "dist", dist, "cur_length", cur_length, "best_i", best_i, "best_j", best_j, "best_value", best_value);
     RLS_GUARD(perm);
     ok(rls_tsp_2opt_best((const double*)p(dist), perm.size(1), (const int64_t*)p(perm), perm.size(0), (const double*)p(cur_length), (int32_t)slices,
                          (int64_t*)p(best_i), (int64_t*)p(best_j), (double*)p(best_value), cur_stream(perm)), "rls_tsp_2opt_best");
@@ -1076,6 +1123,7 @@ void tsp_2opt_delta(const Tensor& dist, const Tensor& perm, const Tensor& i, con
     count(i, "i", perm.size(0));
     count(j, "j", perm.size(0));
     count(delta, "delta", perm.size(0));
+    on_device_of(perm, "dist", dist, "i", i, "j", j, "delta", delta);
     RLS_GUARD(perm);
     ok(rls_tsp_2opt_delta((const float*)p(dist), perm.size(1), (const int64_t*)p(perm), perm.size(0), (const int64_t*)p(i), (const int64_t*)p(j),
                           (float*)p(delta), cur_stream(perm)), "rls_tsp_2opt_delta");
@@ -1103,7 +1151,6 @@ static int64_t isco_flip_step_checks(int64_t g, const Tensor& x, const Tensor& y
     if (mask_out.has_value()) { spin_bytes(*mask_out, "mask_out", false); shape2(*mask_out, "mask_out", B, N); }
     if (scratch.has_value()) {      // the kernel's f32 rows past ~15 900 nodes: a device pointer it writes through
         dev(*scratch, "scratch");
-        same_device(x, *scratch, "scratch");
         TORCH_CHECK(scratch->is_contiguous(), "scratch must be contiguous");
     }
     return B;
@@ -1112,6 +1159,8 @@ void isco_maxcut_step(int64_t g, const Tensor& x, Tensor y_out, const Tensor& pa
                       const OptTensor& u_accept, int64_t seed, int64_t env_offset, const OptTensor& energy_out, const OptTensor& acc_out,
                       const OptTensor& terms_out, const OptTensor& mask_out, const OptTensor& scratch) {
     const int64_t B = isco_flip_step_checks(g, x, y_out, path_length, u_gumbel, u_accept, energy_out, acc_out, terms_out, mask_out, scratch);
+    on_device_of(x, "y_out", y_out, "path_length", path_length, "u_gumbel", u_gumbel, "u_accept", u_accept, "energy_out", energy_out,
+                 "acc_out", acc_out, "terms_out", terms_out, "mask_out", mask_out, "scratch", scratch);
     RLS_GUARD(x);
     ok(rls_isco_maxcut_step(G(g), (const float*)p(x), (float*)p(y_out), B, (const int64_t*)p(path_length), (float)temperature,
                             (const float*)p(u_gumbel), (const float*)p(u_accept), (uint64_t)seed, env_offset, (float*)p(energy_out),
@@ -1122,6 +1171,8 @@ void isco_mis_step(int64_t g, const Tensor& x, Tensor y_out, const Tensor& path_
                    const OptTensor& u_accept, int64_t seed, int64_t env_offset, const OptTensor& energy_out, const OptTensor& acc_out,
                    const OptTensor& terms_out, const OptTensor& mask_out, const OptTensor& scratch) {
     const int64_t B = isco_flip_step_checks(g, x, y_out, path_length, u_gumbel, u_accept, energy_out, acc_out, terms_out, mask_out, scratch);
+    on_device_of(x, "y_out", y_out, "path_length", path_length, "u_gumbel", u_gumbel, "u_accept", u_accept, "energy_out", energy_out,
+                 "acc_out", acc_out, "terms_out", terms_out, "mask_out", mask_out, "scratch", scratch);
     RLS_GUARD(x);
     ok(rls_isco_mis_step(G(g), (const float*)p(x), (float*)p(y_out), B, (const int64_t*)p(path_length), (float)temperature, (float)lam,
                          (const float*)p(u_gumbel), (const float*)p(u_accept), (uint64_t)seed, env_offset, (float*)p(energy_out),
@@ -1132,7 +1183,6 @@ void isco_mis_step(int64_t g, const Tensor& x, Tensor y_out, const Tensor& path_
 static int64_t pisco_shapes(const Tensor& adj, const Tensor& x) {
     dev(adj, "adj", at::kHalf);
     dev(x, "x", at::kHalf);
-    same_device(adj, x, "x");
     TORCH_CHECK(adj.dim() == 2 && adj.size(0) == adj.size(1) && adj.size(0) > 0 && adj.size(0) % 8 == 0,
                 "adj must be [Np, Np] with Np a positive multiple of 8, got ", adj.sizes());
     TORCH_CHECK(x.dim() == 2 && x.size(1) == adj.size(0), "x must be [B, ", adj.size(0), "], got ", x.sizes());
@@ -1141,8 +1191,8 @@ static int64_t pisco_shapes(const Tensor& adj, const Tensor& x) {
 void pisco_product(const Tensor& adj, const Tensor& x, Tensor r_out) {
     const int64_t B = pisco_shapes(adj, x), Np = adj.size(0);
     dev(r_out, "r_out", F32);
-    same_device(x, r_out, "r_out");
     shape2(r_out, "r_out", B, Np);
+    on_device_of(x, "adj", adj, "r_out", r_out);
     RLS_GUARD(x);
     ok(rls_pisco_product((const uint16_t*)p(adj), Np, (const uint16_t*)p(x), B, (float*)p(r_out), cur_stream(x)), "rls_pisco_product");
 }
@@ -1158,7 +1208,6 @@ void pisco_step(const Tensor& adj, const Tensor& x, Tensor y_out, const Tensor& 
     optdev(acc_out, "acc_out", F32);
     optdev(terms_out, "terms_out", F32);
     TORCH_CHECK(y_out.sizes() == x.sizes(), "y_out must have the shape of x");
-    same_device(x, y_out, "y_out");
     count(path_length, "path_length", B);
     TORCH_CHECK(u_gumbel.has_value() == u_accept.has_value(), "u_gumbel and u_accept must be given together");
     if (u_gumbel.has_value()) { shape2(*u_gumbel, "u_gumbel", B, Np); count(*u_accept, "u_accept", B); }
@@ -1167,7 +1216,8 @@ void pisco_step(const Tensor& adj, const Tensor& x, Tensor y_out, const Tensor& 
     if (terms_out.has_value()) shape2(*terms_out, "terms_out", B, 5);
     if (mask_out.has_value()) { spin_bytes(*mask_out, "mask_out", false); shape2(*mask_out, "mask_out", B, Np); }
     dev(scratch, "scratch");
-    same_device(x, scratch, "scratch");
+    on_device_of(x, "adj", adj, "y_out", y_out, "path_length", path_length, "u_gumbel", u_gumbel, "u_accept", u_accept, "energy_out", energy_out,
+                 "acc_out", acc_out, "terms_out", terms_out, "mask_out", mask_out, "scratch", scratch);
     RLS_GUARD(x);
     ok(rls_pisco_step((const uint16_t*)p(adj), Np, (const uint16_t*)p(x), (uint16_t*)p(y_out), B, (const int64_t*)p(path_length),
                       (float)temperature, half_rounding ? 1 : 0, (const float*)p(u_gumbel), (const float*)p(u_accept), (uint64_t)seed,
@@ -1206,6 +1256,9 @@ void isco_tsp_step(const Tensor& dist, const Tensor& nearest, double near_thresh
     if (log_acc_out.has_value()) count(*log_acc_out, "log_acc_out", B);
     if (acc_out.has_value()) count(*acc_out, "acc_out", B);
     if (cur_out.has_value()) shape2(*cur_out, "cur_out", B, N);
+    on_device_of(perm_in, "dist", dist, "nearest", nearest, "random", random, "perm_out", perm_out, "u_partner", u_partner, "r_near", r_near,
+                 "r_rand", r_rand, "u_gumbel", u_gumbel, "u_accept", u_accept, "log_acc_out", log_acc_out, "acc_out", acc_out,
+                 "cur_out", cur_out);
     RLS_GUARD(perm_in);
     ok(rls_isco_tsp_step((const float*)p(dist), N, (const int32_t*)p(nearest), (int32_t)nearest.size(1), (float)near_threshold,
                          (const int32_t*)p(random), (int32_t)random.size(1), (const int64_t*)p(perm_in), (int64_t*)p(perm_out), B,
@@ -1238,6 +1291,7 @@ TORCH_LIBRARY(rlsolver_hip, m) {
     m.def("select_better_rows(Tensor(a!) xs0, Tensor(b!) vs0, Tensor xs1, Tensor vs1, bool if_maximize) -> ()");
     m.def("pick_best_of_repeats(Tensor xs, Tensor vs, int R, bool if_maximize, Tensor(a!) good_xs, Tensor(b!) good_vs) -> ()");
     m.def("copy_rows(Tensor(a!) xs, Tensor(b!)? vs, Tensor dst, Tensor src) -> ()");
+    m.def("copy_rows_bounded(Tensor(a!) xs, Tensor(b!)? vs, Tensor dst, Tensor src) -> ()");
     m.def("best_update(Tensor xs, Tensor vs, bool if_maximize, Tensor(a!) best_x, Tensor(b!) best_v, Tensor(c!) improved, Tensor(d!)? log_v, "
           "int log_index, bool force) -> ()");
     m.def("best_key(Tensor vs, int rank_bits, int low_code, int limit, Tensor(a!) key, Tensor(b!)? index, Tensor(c!) flag) -> ()");
@@ -1324,6 +1378,7 @@ TORCH_LIBRARY_IMPL(rlsolver_hip, CUDA, m) {   // "CUDA" is the HIP dispatch key 
     m.impl("select_better_rows", &select_better_rows);
     m.impl("pick_best_of_repeats", &pick_best_of_repeats);
     m.impl("copy_rows", &copy_rows);
+    m.impl("copy_rows_bounded", &copy_rows_bounded);
     m.impl("best_update", &best_update);
     m.impl("best_key", &best_key);
     m.impl("key_unpack", &key_unpack);

@@ -35,7 +35,7 @@ def evolutionary_replacement(xs: TEN, vs: TEN, low_k: int, if_maximize: bool = T
     """rlsolver/methods/util.py:87-94, in place: the ``low_k`` rows with the best values (sic -- the reference calls
     them ``low_ids``) overwrite ``low_k`` rows drawn without replacement from the others.  The ranking and the draw
     are [B]-sized torch ops (they define how torch's generator is consumed: one randperm(B - low_k)); the row
-    moves are one kernel (rls_copy_rows).  With if_maximize=False the reference indexes a low_k-long tensor with
+    moves are one kernel (rls_copy_rows_bounded).  With if_maximize=False the reference indexes a low_k-long tensor with
     randperm(B - low_k) and raises IndexError unless the draw happens to stay in range: reproduced."""
     B = xs.shape[0]
     rank = vs.argsort()
@@ -51,7 +51,7 @@ def evolutionary_replacement(xs: TEN, vs: TEN, low_k: int, if_maximize: bool = T
     donors = donors.contiguous()
     if xs.dtype in (th.bool, th.uint8) and xs.is_cuda and xs.is_contiguous():
         v64 = vs if (vs.dtype == th.int64 and vs.is_contiguous()) else None
-        ops._t.copy_rows(xs, v64, targets, donors)
+        ops._t.copy_rows_bounded(xs, v64, targets, donors)
         if v64 is None:
             vs[targets] = vs[donors]
     else:
