@@ -1038,6 +1038,15 @@ int rls_pisco_step(const uint16_t* adj, int64_t Np, const uint16_t* x, uint16_t*
                    int64_t env_offset, float* energy_out, float* acc_out, float* terms_out, uint8_t* mask_out, void* scratch,
                    int64_t scratch_bytes, void* stream);
 
+/* [host] The launch rls_isco_maxcut_step / rls_isco_mis_step (dense = 0) or rls_pisco_step (dense != 0, N = Np) make for B samples
+ * of N nodes on a device of `cus` compute units, under the tuning knobs as they stand (csrc/rls_isco_plan.h; no device needed):
+ * out[0] wg (1: a workgroup per sample, 0: a wave per sample), out[1] grows (1: the two f32 rows in the caller's scratch),
+ * out[2] P and out[3] Pw (capacity of the selected-set list of the workgroup / the wave form; a larger selection is ordered by
+ * extraction), out[4] waves (samples per workgroup of the wave form), out[5] lds (dynamic LDS bytes of the chosen form),
+ * out[6] err (RLS_OK, or the code the step returns without launching), out[7] need (LDS bytes of the smallest form: what a
+ * refusal reports).  Returns RLS_OK whenever it answers -- a refusal of the step is out[6], not the return value. */
+int rls_isco_launch_plan(int64_t N, int64_t B, int cus, int dense, int64_t* out);
+
 /* ISCO_TSP.step(x, path_length, temperature)  envs/env_ISCO.py:188-236 in ONE kernel (one wave per env, the tour,
  * its inverse and -- when it fits -- the distance matrix in LDS): path_length times { opt_2 (:238-335: partner
  * city per position from the nearest / random tables, swap delta, ban mask) -> logits = -delta / 2T (banned:

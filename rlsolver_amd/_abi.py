@@ -145,6 +145,7 @@ SIGNATURES = {
                           _P, _P, _P, _P],
     "rls_pisco_product": [_P, _I64, _P, _I64, _P, _P],
     "rls_pisco_step": [_P, _I64, _P, _P, _I64, _P, _F32, C.c_int32, _P, _P, _U64, _I64, _P, _P, _P, _P, _P, _I64, _P],
+    "rls_isco_launch_plan": [_I64, _I64, _INT, _INT, _P],
     "rls_copy_rows": [_P, _P, _I64, _P, _P, _I64, _P],
     "rls_copy_rows_bounded": [_P, _P, _I64, _I64, _P, _P, _I64, _P],
     "rls_best_update": [_P, _P, _INT, _I64, _I64, _INT, _P, _P, _P, _P, _I64, _INT, _P],

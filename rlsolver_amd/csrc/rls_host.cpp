@@ -5,6 +5,7 @@
 #include "rls_host.h"
 #include "rls_subset_plan.h"
 #include "rls_s2vppo_plan.h"
+#include "rls_isco_plan.h"
 #include <cstdarg>
 #include <cstdio>
 #include <algorithm>
@@ -504,6 +505,19 @@ int rls_s2vppo_launch_plan(int64_t B, int64_t max_nodes, int64_t* out) {
     const rls::S2vPlan p = rls::s2vppo_plan(B, max_nodes);
     if (p.err != RLS_OK) return rls::fail(p.err, "s2vppo_launch_plan: B=%lld and max_nodes=%lld must be in [0, 2^31)", (long long)B, (long long)max_nodes);
     out[0] = p.form; out[1] = p.block; out[2] = p.envs; out[3] = p.grid;
+    return RLS_OK;
+}
+
+// ---- ISCO steps on a graph or a dense matrix: the launchers' own planner (rls_isco_plan.h), called as they call it
+int rls_isco_launch_plan(int64_t N, int64_t B, int cus, int dense, int64_t* out) {
+    if (!out) return rls::fail(RLS_EINVAL, "out is NULL");
+    if (N < 1 || N >= (1ll << 31) || B < 0 || cus < 1)
+        return rls::fail(RLS_EINVAL, "isco_launch_plan: N=%lld must be in [1, 2^31), B=%lld >= 0, cus=%d >= 1", (long long)N, (long long)B, cus);
+    if (dense && N % 8 != 0) return rls::fail(RLS_EINVAL, "isco_launch_plan: Np=%lld must be a multiple of 8", (long long)N);
+    const rls::IscoPlan p = dense ? rls::isco_plan_step(rls::isco_rows_bytes(N), N, B, cus, rls::kIscoMinList, false)
+                                  : rls::isco_plan_step(rls::isco_rows_bytes(N), N, B, cus, 1, true);
+    out[0] = p.wg; out[1] = p.grows; out[2] = p.P; out[3] = p.Pw; out[4] = p.waves; out[5] = (int64_t)p.lds; out[6] = p.err;
+    out[7] = (int64_t)p.need;
     return RLS_OK;
 }
 

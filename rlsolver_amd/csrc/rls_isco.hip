@@ -237,11 +237,16 @@ __device__ __forceinline__ int isco_compact_wg(const float* pert, int64_t N, uin
 
 // The list sorted by perturbed value, descending, by ONE wave: padded to a power of two, bitonic.
 // TIE: equal keys order by node id (lowest first, as the extraction), so that the result does not depend on the compaction order.
+// A pad carries the key -inf and kIscoPadIdx, an index that orders after every node: a real entry's key is -inf too when its
+// draw is u = 0 (isco_unit returns it once in 2^24 draws), and a pad in front of it would hand index arithmetic a node that
+// does not exist.  Among keys of -inf the lower index goes first in both variants, so every pad ends up behind all `count`
+// real entries; finite keys never compare equal to a pad's and order exactly as they did.
+constexpr int32_t kIscoPadIdx = 0x7FFFFFFF;
 template <bool TIE>
 __device__ __forceinline__ void isco_sort_list(float* skey, int32_t* sidx, int count, int lane) {
     int P2 = 1;
     while (P2 < count) P2 <<= 1;
-    for (int k = count + lane; k < P2; k += kWave) { skey[k] = -INFINITY; sidx[k] = -1; }
+    for (int k = count + lane; k < P2; k += kWave) { skey[k] = -INFINITY; sidx[k] = kIscoPadIdx; }
     lds_fence();
     for (int size = 2; size <= P2; size <<= 1) {
         for (int stride = size >> 1; stride >= 1; stride >>= 1) {
@@ -258,7 +263,8 @@ __device__ __forceinline__ void isco_sort_list(float* skey, int32_t* sidx, int c
                         sidx[lo] = i1; sidx[hi] = i0;
                     }
                 } else {
-                    if ((k0 < k1) == desc) {
+                    const bool lt = (k0 < k1) || (k1 == -INFINITY && k0 == k1 && sidx[lo] > sidx[hi]);
+                    if (lt == desc) {
                         skey[lo] = k1; skey[hi] = k0;
                         const int t0 = sidx[lo]; sidx[lo] = sidx[hi]; sidx[hi] = t0;
                     }

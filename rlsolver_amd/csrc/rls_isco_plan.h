@@ -67,7 +67,7 @@ inline IscoPlan isco_plan_step(size_t rows, int64_t N, int64_t B, int cus, int m
         return p;
     }
     // capacity of the selected-set list in LDS: a power of two >= N while that fits (N <= 4096: as before), else the largest
-    // power of two the rows leave room for, at least 64 (N = 10^4: 4096; N = 15 000: 512) -- a larger selection takes the
+    // power of two the rows leave room for, at least 64 (N = 10^4: 4096; N = 15 000: 1024; N = 15 500: 512) -- a larger selection takes the
     // extraction path.  The rows themselves (two byte rows, two f32 rows) bound N at ~15 900.  (The smallest list fits, checked
     // above, so the list this leaves always does.)
     int P = 1;

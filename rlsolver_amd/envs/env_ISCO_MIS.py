@@ -51,6 +51,7 @@ class ISCO_MIS(Sharded):
     # env_ISCO.py:106-109 and the scratch of rows past the LDS: the same samples, the same rows (rls_isco_maxcut_scratch_bytes)
     random_gen_init_sample = ISCO_maxcut.random_gen_init_sample
     _step_scratch = ISCO_maxcut._step_scratch
+    launch_plan = ISCO_maxcut.launch_plan
 
     def step(self, x, path_length, temperature, draws: Optional[dict] = None, want_terms: bool = False):
         """env_ISCO.py:111-119 -> (y f32 [B, N], ll_y * temperature f32 [B], acceptance probability f32 [B]).

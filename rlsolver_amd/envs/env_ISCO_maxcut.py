@@ -20,6 +20,19 @@ from ..ops import _check, _s64, _t
 from ..seeding import Sharded
 
 
+def isco_launch_plan(N: int, B: int, cus: int, dense: bool) -> dict:
+    """rls_isco_launch_plan as a dict (a host query, no device needed): the launch of the graph steps, or of the dense step
+    (``dense``, N = Np), for B samples of N nodes on ``cus`` compute units.  ``form``: "wave" (a wave per sample, list capacity
+    ``Pw``, ``waves`` samples per workgroup), "workgroup" (list capacity ``P``) or "workgroup, rows in scratch"; ``err`` != 0: the
+    code the step returns without launching, ``need`` the LDS bytes it reports."""
+    import ctypes as C
+    out = (C.c_int64 * 8)()
+    _abi.call("rls_isco_launch_plan", int(N), int(B), int(cus), int(bool(dense)), C.cast(out, C.c_void_p))
+    wg, grows, P, Pw, waves, lds, err, need = (int(v) for v in out)
+    form = "workgroup, rows in scratch" if grows else "workgroup" if wg else "wave"
+    return dict(form=form, wg=bool(wg), grows=bool(grows), P=P, Pw=Pw, waves=waves, lds=lds, err=err, need=need)
+
+
 class ISCO_maxcut(Sharded):
     def __init__(self, params_dict, batch_size: int = 1, device=None, chain_length: int = 200,
                  init_temperature: float = 1.0, final_temperature: float = 0.0, env_offset: int = 0, seed: Optional[int] = None):
@@ -59,6 +72,11 @@ class ISCO_maxcut(Sharded):
         if have is None or have.numel() < need:
             have = self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
         return have
+
+    def launch_plan(self, B: int) -> dict:
+        """What ``step`` launches for B samples on this device under the tuning knobs as they stand (rls_isco_launch_plan: the
+        launcher's own planner, csrc/rls_isco_plan.h)."""
+        return isco_launch_plan(self.max_num_nodes, B, torch.cuda.get_device_properties(self.device).multi_processor_count, False)
 
     def step(self, x, path_length, temperature, draws: Optional[dict] = None, want_terms: bool = False):
         """env_ISCO.py:26-35 -> (y f32 [B, N], ll_y * temperature f32 [B], acceptance probability f32 [B]).

@@ -134,6 +134,12 @@ class PISCO_maxcut(Sharded):
             self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._scratch
 
+    def launch_plan(self, B: int) -> dict:
+        """What ``step`` launches after the product for B samples on this device under the tuning knobs as they stand
+        (rls_isco_launch_plan, dense: the launcher's own planner, csrc/rls_isco_plan.h)."""
+        from .env_ISCO_maxcut import isco_launch_plan
+        return isco_launch_plan(self.padded_num_nodes, B, torch.cuda.get_device_properties(self.device).multi_processor_count, True)
+
     def _sample(self, x, name="x"):
         x = _check(x.contiguous(), name, (torch.float16,), self.device)
         if x.dim() != 2 or x.shape[1] != self.padded_num_nodes:

@@ -295,6 +295,10 @@ static void run_isco_plans(std::mt19937_64& rng) {
             for (int dense = 0; dense < 2; ++dense) {
                 const int64_t n = dense ? (N + 7) / 8 * 8 : N;
                 const rls::IscoPlan p = rls::isco_plan_step(rls::isco_rows_bytes(n), n, B, cus, dense ? rls::kIscoMinList : 1, !dense);
+                int64_t q[8] = {-1, -1, -1, -1, -1, -1, -1, -1};       // the host query answers with the same plan
+                CHECK(rls_isco_launch_plan(n, B, cus, dense, q) == RLS_OK && q[0] == p.wg && q[1] == p.grows && q[2] == p.P && q[3] == p.Pw &&
+                          q[4] == p.waves && q[5] == (int64_t)p.lds && q[6] == p.err && q[7] == (int64_t)p.need,
+                      "rls_isco_launch_plan N %lld B %lld dense %d differs from isco_plan_step", (long long)n, (long long)B, dense);
                 if (p.err != RLS_OK) {
                     CHECK(p.err == RLS_EUNSUPPORTED && p.need > (size_t)rls::kLdsBytes, "ISCO plan N %lld refused at %zu B", (long long)n, p.need);
                     continue;
