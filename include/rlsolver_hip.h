@@ -522,6 +522,33 @@ int rls_spin_step_dense(const void* matrix, const void* max_local, const rls_spi
 int rls_rand_couplings(void* matrix, int state_bytes, int64_t B, int64_t N, int32_t kind, double p_connection, int32_t m_insertion_edges,
                        int32_t edge_type, uint64_t seed, int64_t env_offset, void* stream);
 
+/* The exact optimum of a spin system by enumeration of all 2^N states: what SpinSystemBase.calculate_best_energy() and its
+ * helper _calc_over_range(i0, iMax) of ECO_S2V/src/envs/spinsystem.py:278-324, 615-651 compute (dqn.py:586 and dqn_PECO.py:546
+ * call env.calculate_best()[0] for their "distance from optimum" score).  State index i in [0, 2^N) is read MSB first: node k's
+ * spin is +1 iff bit N-1-k of i is set (np.binary_repr(i, width=N)).  1 <= N <= 48; couplings symmetric with off-diagonal entries
+ * in {-1, 0, +1} and any diagonal (E = -s'Ws / 2 = -tr(W) / 2 + E_off; the trace term is the caller's).
+ *
+ * rls_spin_exhaustive_pack replaces `matrix = self.matrix.astype('float64')` of _calc_over_range (spinsystem.py:620): matrix T
+ * [G, N, N] (state_bytes 4 | 8) -> pos, neg uint64 [G, N]: bit N-1-j of pos[g, p] is set iff W_pj == +1 and j != p, of neg[g, p]
+ * iff W_pj == -1 and j != p; flags uint8 [G]: bit 0 = an off-diagonal entry outside {-1, 0, +1}, bit 1 = asymmetric.  All three
+ * are results only (written for every graph). */
+int rls_spin_exhaustive_pack(const void* matrix, int state_bytes, int64_t G, int64_t N, uint64_t* pos, uint64_t* neg, uint8_t* flags,
+                             void* stream);
+
+/* rls_spin_exhaustive replaces the loop of __calc_over_range_jit (spinsystem.py:640-651) over the states i0 <= i < i1
+ * (0 <= i0 < i1 <= 2^N): key[g] = min(key[g], ((E_off(i) + 4096) << 48) | i) with E_off = -sum_{p<q} W_pq s_p s_q as int32, one
+ * 64-bit atomic minimum per workgroup and graph.  key uint64 [G] is read and written: the caller starts it at INT64_MAX, and
+ * chained launches over sub-ranges, or other ranks, fold into the same key -- the lexicographic minimum (lowest energy, then
+ * lowest index: the reference's strict `<` in ascending order) does not depend on launch geometry or scheduling.  The maximum of
+ * E_off (and so the maximum cut, (sum_{p<q} W_pq + E_off) / 2) is the same call with pos and neg swapped.  The 13-bit field holds
+ * every |E_off| <= 2256, the most arbitrary masks can produce at N = 48; masks not made by rls_spin_exhaustive_pack give a
+ * meaningless key and never an access outside pos, neg or key.
+ * A thread owns aligned chunks of 2^L consecutive indices (L = min(N, 10)): the energy splits into the part among the high N - L
+ * nodes (once per chunk, popcounts of masked words), the part among the low L nodes (a table of 2^L entries per workgroup, in
+ * reflected Gray order, shared by every chunk) and the cross term, which one add per Gray step keeps current. */
+int rls_spin_exhaustive(const uint64_t* pos, const uint64_t* neg, int64_t G, int64_t N, int64_t i0, int64_t i1, uint64_t* key,
+                        void* stream);
+
 /* get_observation()  ECO_S2V/src/envs/spinsystem_PECO.py:455,497 (cat(state, matrix_obs)) and spinsystem.py:484-495
  * (vstack(state, matrix)): out T [B, num_rows + N, N] = the num_rows observable rows as the reference's state tensor holds
  * them after step_index steps of the episode (row 0 mapped from signed spins to (1 - s) / 2 when binary_basis,

@@ -621,6 +621,38 @@ void rand_couplings(Tensor matrix, int64_t kind, double p_connection, int64_t m_
     ok(rls_rand_couplings(p(matrix), matrix.scalar_type() == F64 ? 8 : 4, matrix.size(0), matrix.size(1), (int32_t)kind, p_connection,
                           (int32_t)m_insertion_edges, (int32_t)edge_type, (uint64_t)seed, env_offset, cur_stream(matrix)), "rls_rand_couplings");
 }
+// exact optimum by enumeration (csrc/rls_exhaustive.hip): int64 tensors carry the uint64 masks and keys
+void spin_exhaustive_pack(const Tensor& matrix, Tensor pos, Tensor neg, Tensor flags) {
+    dev(matrix, "matrix");
+    TORCH_CHECK(matrix.scalar_type() == F32 || matrix.scalar_type() == F64, "matrix must be float32 or float64, got ", matrix.scalar_type());
+    TORCH_CHECK(matrix.dim() == 3 && matrix.size(1) == matrix.size(2), "matrix must be [G, N, N], got ", matrix.sizes());
+    const int64_t G = matrix.size(0), N = matrix.size(1);
+    TORCH_CHECK(N >= 1 && N <= 48, "spin_exhaustive_pack: N = ", N, " outside [1, 48]");
+    dev(pos, "pos", I64);
+    dev(neg, "neg", I64);
+    dev(flags, "flags", U8);
+    shape2(pos, "pos", G, N);
+    shape2(neg, "neg", G, N);
+    TORCH_CHECK(flags.dim() == 1 && flags.size(0) == G, "flags must be [", G, "], got ", flags.sizes());
+    on_device_of(matrix, "pos", pos, "neg", neg, "flags", flags);
+    RLS_GUARD(matrix);
+    ok(rls_spin_exhaustive_pack(p(matrix), matrix.scalar_type() == F64 ? 8 : 4, G, N, (uint64_t*)p(pos), (uint64_t*)p(neg), (uint8_t*)p(flags),
+                                cur_stream(matrix)), "rls_spin_exhaustive_pack");
+}
+void spin_exhaustive(const Tensor& pos, const Tensor& neg, int64_t i0, int64_t i1, Tensor key) {
+    dev(pos, "pos", I64);
+    dev(neg, "neg", I64);
+    dev(key, "key", I64);
+    TORCH_CHECK(pos.dim() == 2, "pos must be [G, N], got ", pos.sizes());
+    const int64_t G = pos.size(0), N = pos.size(1);
+    TORCH_CHECK(N >= 1 && N <= 48, "spin_exhaustive: N = ", N, " outside [1, 48]");
+    shape2(neg, "neg", G, N);
+    TORCH_CHECK(key.dim() == 1 && key.size(0) == G, "key must be [", G, "], got ", key.sizes());
+    TORCH_CHECK(i0 >= 0 && i0 < i1 && i1 <= ((int64_t)1 << N), "spin_exhaustive: [i0, i1) = [", i0, ", ", i1, ") must be non-empty and inside [0, 2^", N, "]");
+    on_device_of(pos, "neg", neg, "key", key);
+    RLS_GUARD(pos);
+    ok(rls_spin_exhaustive((const uint64_t*)p(pos), (const uint64_t*)p(neg), G, N, i0, i1, (uint64_t*)p(key), cur_stream(pos)), "rls_spin_exhaustive");
+}
 void spin_reset_dense(const Tensor& matrix, int64_t env, const Tensor& state, const Tensor& row_index, Tensor max_local, Tensor weight_sum,
                       Tensor flags) {
     const int sb = state_bytes(state, SE(env));
@@ -1309,6 +1341,8 @@ TORCH_LIBRARY(rlsolver_hip, m) {
     m.def("spin_observation(int env, Tensor state, Tensor row_index, int step_index, Tensor? matrix, bool binary_basis, Tensor(a!) out) -> ()");
     m.def("spin_materialize(int env, Tensor(a!) state, Tensor row_index, int step_index) -> ()");
     m.def("rand_couplings(Tensor(a!) matrix, int kind, float p_connection, int m_insertion_edges, int edge_type, int seed, int env_offset) -> ()");
+    m.def("spin_exhaustive_pack(Tensor matrix, Tensor(a!) pos, Tensor(b!) neg, Tensor(c!) flags) -> ()");
+    m.def("spin_exhaustive(Tensor pos, Tensor neg, int i0, int i1, Tensor(a!) key) -> ()");
     m.def("spin_reset_dense(Tensor matrix, int env, Tensor(a!) state, Tensor row_index, Tensor(b!) max_local, Tensor(c!) weight_sum, Tensor(d!) flags) -> ()");
     m.def("spin_step_dense(Tensor matrix, Tensor max_local, int env, Tensor(a!) state, Tensor row_index, Tensor action, Tensor(b!) reward, "
           "Tensor(c!)? visited_new, float termination_value, int reward_mode, float reward_div, int hist_len, bool use_stag, "
@@ -1395,6 +1429,8 @@ TORCH_LIBRARY_IMPL(rlsolver_hip, CUDA, m) {   // "CUDA" is the HIP dispatch key 
     m.impl("spin_observation", &spin_observation);
     m.impl("spin_materialize", &spin_materialize);
     m.impl("rand_couplings", &rand_couplings);
+    m.impl("spin_exhaustive_pack", &spin_exhaustive_pack);
+    m.impl("spin_exhaustive", &spin_exhaustive);
     m.impl("spin_reset_dense", &spin_reset_dense);
     m.impl("spin_step_dense", &spin_step_dense);
     m.impl("spin_step", &spin_step);

@@ -88,6 +88,37 @@ _ROW_ORDER = [Observable.IMMEDIATE_REWARD_AVAILABLE, Observable.TIME_SINCE_FLIP,
               Observable.DISTANCE_FROM_BEST_SCORE, Observable.DISTANCE_FROM_BEST_STATE]
 _REWARD_MODE = {RewardSignal.DENSE: 0, RewardSignal.BLS: 1, RewardSignal.CUSTOM_BLS: 2}
 
+EXHAUSTIVE_DEFAULT_MAX_SPINS = 40      # what calculate_best* enumerate unasked: 2^40 states; the caller raises max_spins up to 48
+
+
+class ExhaustiveOptimum:
+    """The answer of exhaustive_optimum, per graph, float64 / int64 on the device: ``energy`` = -s'Ws / 2 of the optimal state,
+    ``cut`` = its cut, ``index`` = the first state that attains the optimum, ``spins`` its signed spins [G, N]."""
+
+    def __init__(self, energy, cut, index, spins):
+        self.energy, self.cut, self.index, self.spins = energy, cut, index, spins
+
+
+def exhaustive_optimum(matrix, i0=0, i1=None, maximize=False, max_spins=EXHAUSTIVE_DEFAULT_MAX_SPINS) -> ExhaustiveOptimum:
+    """The state of minimum (``maximize``: maximum) energy E = -s'Ws / 2 among the states i0 <= i < i1 of every graph of ``matrix``
+    [G, N, N], by enumeration (ops.spin_exhaustive: one kernel over the range).  The maximum of E is the maximum cut:
+    cut = (sum_{p<q} W_pq + E_off) / 2 with E_off = E + tr(W) / 2, exact.  Couplings: symmetric, off-diagonal entries in {-1, 0, +1}."""
+    N = int(matrix.shape[-1])
+    if not 1 <= int(max_spins) <= ops.EXHAUSTIVE_MAX_SPINS:
+        raise ValueError(f"max_spins must be in [1, {ops.EXHAUSTIVE_MAX_SPINS}], got {max_spins}")
+    if N > int(max_spins):
+        raise ValueError(f"n_spins = {N}: 2^{N} states are above max_spins = {max_spins}; raise max_spins (at most "
+                         f"{ops.EXHAUSTIVE_MAX_SPINS}) to enumerate them")
+    key, half_trace = ops.spin_exhaustive(matrix, i0, i1, maximize)
+    e_off, index = ops.exhaustive_key_decode(key)
+    if maximize:
+        e_off = -e_off                                             # the kernel ran on -W
+    upper = torch.triu(matrix.to(torch.float64), diagonal=1).sum(dim=(1, 2))
+    shifts = torch.arange(N - 1, -1, -1, device=key.device, dtype=torch.int64)
+    spins = (2 * ((index[:, None] >> shifts) & 1) - 1).to(torch.float64)
+    e_off = e_off.to(torch.float64)
+    return ExhaustiveOptimum(e_off - half_trace, (upper + e_off) / 2, index, spins)
+
 
 class SpinSystem(Sharded):
     class _ActionSpace:
@@ -418,6 +449,37 @@ class SpinSystem(Sharded):
     def get_best_cut(self):
         return self.best_score
 
+    # ---- the exact optimum by enumeration of all 2^N states (rls_spin_exhaustive; spinsystem.py:278-324, 615-651)
+    def _exhaustive_matrix(self):
+        m = self.matrix
+        return m if m.dim() == 3 else m.unsqueeze(0)
+
+    def _exhaustive_out(self, first, spins):
+        """[G] / [G, N] float64 -> [B] / [B, N] in the env's dtype (a shared graph answers for every env)."""
+        B = self.num_envs
+        return first.to(self.dtype).expand(B).contiguous(), spins.to(self.dtype).expand(B, -1).contiguous()
+
+    def _calc_over_range(self, i0, iMax, max_spins=EXHAUSTIVE_DEFAULT_MAX_SPINS):
+        """spinsystem.py:615-621 -> (the minimum of E = -s'Ws / 2 over the states i0 <= i < iMax [B], the FIRST state that attains it
+        as signed spins [B, N]); state i is np.binary_repr(i, width=n_spins), node 0 first.  One kernel over the range."""
+        r = exhaustive_optimum(self._exhaustive_matrix(), i0, iMax, False, max_spins)
+        return self._exhaustive_out(r.energy, r.spins)
+
+    def calculate_best_energy(self, max_spins=EXHAUSTIVE_DEFAULT_MAX_SPINS):
+        """spinsystem.py:278-324 as written: the minimum-energy state of all 2^n_spins, its spins in the env's ``spin_basis``, and
+        under OptimisationTarget.CUT (the batched env's only target) that state's CUT in place of its energy.  Runs for every
+        n_spins >= 1: the reference raises for n_spins <= 10 (an undefined calculate_best_brute) and, on current numpy, above
+        (a float count given to np.linspace) -- recorded in tests/golden/spin_exhaustive.npz.  ``max_spins`` (default 40, at
+        most 48) refuses an accidental 2^48 job."""
+        r = exhaustive_optimum(self._exhaustive_matrix(), 0, None, False, max_spins)
+        return self._exhaustive_out(r.cut, r.spins if self.spin_basis == SpinBasis.SIGNED else (1 - r.spins) / 2)
+
+    def calculate_best(self, max_spins=EXHAUSTIVE_DEFAULT_MAX_SPINS):
+        """What the agents call for their "distance from optimum" score (dqn_PECO.py:546: env.calculate_best()[0]): the optimum of
+        the env's target -- the MAXIMUM cut [B] and the first state that attains it [B, N] in the env's ``spin_basis``."""
+        r = exhaustive_optimum(self._exhaustive_matrix(), 0, None, True, max_spins)
+        return self._exhaustive_out(r.cut, r.spins if self.spin_basis == SpinBasis.SIGNED else (1 - r.spins) / 2)
+
     # ---- checkpoint of the env state (SURVEY.md section 5): everything a later step depends on
     _STATE_KEYS = ("_state", "_delta", "score", "best_score", "best_spins", "_num_nonpos", "_dist_best", "_last_flip", "_scalars")
     _DENSE_KEYS = ("_matrix", "max_local_reward_available_", "_weight_sum_env")
@@ -703,6 +765,36 @@ class SpinSystemUnbiased:
         if self._energy:                                              # spinsystem.py:609-613
             raise NotImplementedError("Can't return best cut when optimisation target is set to energy.")
         return self.best_score
+
+    # ---- the exact optimum by enumeration (rls_spin_exhaustive): the reference's own post-processing, spinsystem.py:278-324
+    def _exhaustive(self, i0, i1, maximize, max_spins):
+        m = torch.as_tensor(np.ascontiguousarray(self.matrix, dtype=np.float64), device=self._env.device)[None]
+        return exhaustive_optimum(m, i0, i1, maximize, max_spins)
+
+    def _best_out(self, r: "ExhaustiveOptimum"):
+        spins = r.spins[0].cpu().numpy()
+        if self._env.spin_basis == SpinBasis.BINARY:
+            spins = (1 - spins) / 2                       # convert {1,-1} --> {0,1} (:309-313)
+        return float(r.cut[0] if self.optimisation_target == OptimisationTarget.CUT else r.energy[0]), spins
+
+    def _calc_over_range(self, i0, iMax, max_spins=EXHAUSTIVE_DEFAULT_MAX_SPINS):
+        """spinsystem.py:615-621, 640-651 -> (the minimum of E = -s'Ws / 2 over the states i0 <= i < iMax, the FIRST state that
+        attains it as signed spins f64 [N]); state i is np.binary_repr(i, width=n_spins), node 0 first."""
+        r = self._exhaustive(int(i0), int(iMax), False, max_spins)
+        return float(r.energy[0]), r.spins[0].cpu().numpy()
+
+    def calculate_best_energy(self, max_spins=EXHAUSTIVE_DEFAULT_MAX_SPINS):
+        """spinsystem.py:278-324 as written: the minimum-energy state of all 2^n_spins, its spins in the env's ``spin_basis``; under
+        OptimisationTarget.CUT the first value is that state's CUT, under ENERGY its energy.  Runs for every n_spins >= 1: the
+        reference raises for n_spins <= 10 (an undefined calculate_best_brute) and, on current numpy, above (a float count given
+        to np.linspace) -- both recorded in tests/golden/spin_exhaustive.npz.  ``max_spins`` (default 40, at most 48) refuses an
+        accidental 2^48 job."""
+        return self._best_out(self._exhaustive(0, None, False, max_spins))
+
+    def calculate_best(self, max_spins=EXHAUSTIVE_DEFAULT_MAX_SPINS):
+        """What the agents call for their "distance from optimum" score (dqn.py:586: env.calculate_best()[0]): the optimum of the
+        env's target -- the MAXIMUM cut and the first state that attains it under CUT, the minimum energy under ENERGY."""
+        return self._best_out(self._exhaustive(0, None, self.optimisation_target == OptimisationTarget.CUT, max_spins))
 
     def get_allowed_action_states(self):
         """spinsystem.py:514-527: both spin values while spins are reversible, else the value of a spin not flipped yet."""

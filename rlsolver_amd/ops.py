@@ -444,8 +444,101 @@ def rand_actions(B: int, N: int, seed: int, step: int, device, env_offset: int =
     return out
 
 
+# ---- exact optimum of a spin system by enumeration (rls_spin_exhaustive_pack / rls_spin_exhaustive)
+EXHAUSTIVE_MAX_SPINS = 48                       # the index field of the key
+EXHAUSTIVE_KEY_BIAS = 4096                      # key = ((E_off + bias) << 48) | index
+EXHAUSTIVE_KEY_EMPTY = (1 << 63) - 1            # what a key starts at: above every real key
+EXHAUSTIVE_STATES_PER_LAUNCH = 1 << 34          # (graph, state) pairs of one launch; DESIGN.md section 4 has the measurement behind it
+
+
+def split_range(total: int, rank: int, world: int):
+    """(lo, hi) of the contiguous slice of [0, total) that rank `rank` of `world` enumerates: the slices of ranks 0 .. world - 1
+    cover [0, total) in order, without gap or overlap, and differ in length by at most one state (a slice may be empty)."""
+    total, rank, world = int(total), int(rank), int(world)
+    if total < 0 or world < 1 or not 0 <= rank < world:
+        raise ValueError(f"split_range: total {total}, rank {rank}, world {world}")
+    return total * rank // world, total * (rank + 1) // world
+
+
+def exhaustive_key_encode(e_off, index):
+    """The key of state `index` with off-diagonal energy `e_off` (ints, numpy int64 arrays or int64 tensors)."""
+    return ((e_off + EXHAUSTIVE_KEY_BIAS) << 48) | index
+
+
+def exhaustive_key_decode(key):
+    """key -> (E_off, state index); the inverse of exhaustive_key_encode."""
+    return (key >> 48) - EXHAUSTIVE_KEY_BIAS, key & ((1 << 48) - 1)
+
+
+def spin_exhaustive_pack(matrix: TEN):
+    """matrix f32 / f64 [G, N, N] -> (pos, neg int64 [G, N] holding the uint64 masks, flags uint8 [G]); include/rlsolver_hip.h."""
+    _check(matrix, "matrix", (torch.float32, torch.float64))
+    if matrix.dim() != 3 or matrix.shape[1] != matrix.shape[2]:
+        raise ValueError(f"matrix must be [G, N, N], got {tuple(matrix.shape)}")
+    G, N = int(matrix.shape[0]), int(matrix.shape[1])
+    if not 1 <= N <= EXHAUSTIVE_MAX_SPINS:
+        raise ValueError(f"exhaustive enumeration covers 1 <= N <= {EXHAUSTIVE_MAX_SPINS} spins, got N = {N}")
+    pos = torch.empty((G, N), dtype=torch.int64, device=matrix.device)
+    neg = torch.empty_like(pos)
+    flags = torch.empty(G, dtype=torch.uint8, device=matrix.device)
+    _t.spin_exhaustive_pack(matrix, pos, neg, flags)
+    return pos, neg, flags
+
+
+def spin_exhaustive(matrix: TEN, i0: int = 0, i1: Optional[int] = None, maximize: bool = False,
+                    states_per_launch: int = EXHAUSTIVE_STATES_PER_LAUNCH, group=None, key: Optional[TEN] = None):
+    """The minimum (``maximize``: the maximum) of E = -s'Ws / 2 over the states i0 <= i < i1 (default: all 2^N) of every graph of
+    ``matrix`` [G, N, N] (or [N, N]) -> (key int64 [G], trace / 2 f64 [G]).  State i is read MSB first (node k is +1 iff bit
+    N-1-k of i is set); exhaustive_key_decode(key) = (E_off, the FIRST state that attains it), E = E_off - trace / 2 -- under
+    ``maximize`` the key holds -E_off (the masks are swapped: W -> -W), so E = -E_off - trace / 2.  cut = (sum_{p<q} W_pq + E_off) / 2.
+
+    The matrix must be symmetric with off-diagonal entries in {-1, 0, +1} (any diagonal): ValueError names the first graph that is
+    not (one host read of the flags; this is no step path).  The range is cut into launches of at most ``states_per_launch``
+    (graph, state) pairs.  ``group``: this rank enumerates its split_range slice of [i0, i1) and the keys meet in one
+    all_reduce(MIN).  ``key``: an int64 [G] tensor to fold into (it starts at EXHAUSTIVE_KEY_EMPTY) instead of a fresh one."""
+    if isinstance(matrix, torch.Tensor) and matrix.dim() == 2:
+        matrix = matrix.unsqueeze(0)
+    pos, neg, flags = spin_exhaustive_pack(matrix)
+    G, N = pos.shape
+    i1 = (1 << N) if i1 is None else int(i1)
+    i0, per = int(i0), int(states_per_launch)
+    if not (0 <= i0 < i1 <= (1 << N)):
+        raise ValueError(f"the range [{i0}, {i1}) must be non-empty and inside [0, 2^{N}]")
+    if per < 1:
+        raise ValueError(f"states_per_launch must be >= 1, got {per}")
+    if key is not None:
+        _check(key, "key", (torch.int64,), matrix.device, (G,))
+    bad = torch.nonzero(flags).flatten()[:1].tolist()            # the host read
+    if bad:
+        f = int(flags[bad[0]])
+        what = "an off-diagonal entry outside {-1, 0, +1}" if f & 1 else "an asymmetric matrix"
+        raise ValueError(f"spin_exhaustive: graph {bad[0]} has {what}; the couplings must be symmetric with off-diagonal entries in "
+                         "{-1, 0, +1}")
+    if key is None:
+        key = torch.full((G,), EXHAUSTIVE_KEY_EMPTY, dtype=torch.int64, device=matrix.device)
+    lo, hi = i0, i1
+    if group is not None:
+        import torch.distributed as tdist
+        a, b = split_range(i1 - i0, tdist.get_rank(group), tdist.get_world_size(group))
+        lo, hi = i0 + a, i0 + b
+    step = max(1, per // max(G, 1))
+    if step >= 1024:
+        step -= step % 1024                                      # whole chunks: only the ends of the range are cut ones
+    if maximize:
+        pos, neg = neg, pos
+    while lo < hi and G:
+        nxt = min(lo + step, hi)
+        _t.spin_exhaustive(pos, neg, lo, nxt, key)
+        lo = nxt
+    if group is not None:
+        from . import dist as _dist
+        _dist._all_reduce(key, tdist.ReduceOp.MIN, group)
+    half_trace = torch.diagonal(matrix, dim1=1, dim2=2).to(torch.float64).sum(dim=1) / 2
+    return key, half_trace
+
+
 # ---- L2A: sub_set_sampling (rls_sub_set_sampling), the candidates of one policy step
-SUB_SET_SAMPLING_MAX_NODES = 20344      # RLS_SUB_SET_SAMPLING_MAX_NODES: what one sim's rows take of the LDS
+SUB_SET_SAMPLING_MAX_NODES = 20344     # RLS_SUB_SET_SAMPLING_MAX_NODES: what one sim's rows take of the LDS
 
 
 def sub_set_sampling_supported(S: int, N: int, R: int, top_k: int) -> bool:

@@ -56,6 +56,7 @@ DEVICE_ENTRY_POINTS = [
     "mcpg_local_search_levels", "mcpg_pick_best", "mcpg_merge_best", "mcpg_value_bit_sums", "mcpg_pack_chains", "mcpg_unpack_chains",
     "qubo_local_search_value", "qubo_sparse_local_search_value", "tsp_tour_length", "tsp_swap_delta_all", "tsp_apply_swap", "tsp_2opt_delta", "tsp_2opt_best", "isco_maxcut_step",
     "isco_mis_step", "isco_tsp_step", "pisco_product", "pisco_step", "maxsat_local_search", "cheeger_local_search", "maxcut_edge_local_search", "mimo_local_search", "sub_set_sampling", "s2vppo_step", "s2vppo_reset",
+    "spin_exhaustive_pack", "spin_exhaustive",
 ]
 # declared in the header but not device work: host-side schedule builders and queries (plain C calls, no op)
 HOST_ENTRY_POINTS = [
