@@ -321,6 +321,32 @@ int rls_maxcut_ls_normals(float* out, int64_t B, int64_t N, uint64_t seed, int64
 int rls_maxcut_ls_slices(const rls_graph* g, int64_t B, int32_t ws_bytes);
 /* 1 when the two entry points above cover this graph / num_spin, else 0 (callers then keep the torch ops + K6). */
 int rls_maxcut_ls_rounds_supported(const rls_graph* g, int32_t num_spin);
+/* [host] The launches rls_maxcut_local_search / _ls_threshold / _ls_propose / _ls_rounds (`what`) would make, in order: the launchers'
+ * own planner (csrc/rls_ls_plan.h), nothing is launched and no pointer of *g is followed -- what tests pin the launch policy with,
+ * without a GPU.  ws_pitch in entries (0 = N); `flags`: which buffers are NOT on a 16-byte base, or absent; scratch_bytes as the entry
+ * point gets it; `cus`: compute units to plan for, <= 0 = the current device's.  Up to `cap` launches are written to out, info gets
+ * their number and, for a refused call, the code and the text the entry point gives (then no launches).  The four host queries above
+ * are views of the same planner.  Additive (ABI 12). */
+enum { RLS_LS_PLAN_FUSED = 0, RLS_LS_PLAN_THRESHOLD = 1, RLS_LS_PLAN_PROPOSE = 2, RLS_LS_PLAN_ROUNDS = 3 };
+enum { RLS_LS_PLAN_X_UNALIGNED = 1, RLS_LS_PLAN_NOISE_UNALIGNED = 2, RLS_LS_PLAN_SCRATCH_UNALIGNED = 4, RLS_LS_PLAN_NO_SCRATCH = 8 };
+typedef struct rls_ls_launch {
+    int32_t kernel;   /* 0 k_maxcut_local_search<true, WT, planes, waves>, 1 k_ls_threshold<WT, sd_lds>, 2 k_ls_threshold_merge, 3 k_ls_mask<WT, sd_lds>,
+                       * 4 k_ls_propose<WT, planes, sd_lds, premask>, 5 k_ls_apply_rounds<planes, waves>, 6 k_ls_apply_rounds32<planes, waves>,
+                       * 7 a call of rls_maxcut_propose_accept on the mask words of round `first_round` */
+    int32_t ws_bytes, planes, waves, sd_lds, premask;   /* template arguments (WT = int8_t / int16_t by ws_bytes); 0 where the kernel has none */
+    uint32_t grid[3], block;
+    int64_t lds;                                        /* dynamic LDS bytes */
+    int32_t batched, x_aligned, stage, rounds;          /* runtime ints of the kernel: sweep schedule (0), aligned rows (0, 4, 5, 6), has-stage (5, 6),
+                                                         * rounds per launch (3: grid[2], 5, 6; 2: the slices it merges) */
+    int32_t first_round;                                /* the launch's first draw, counted from the call's */
+    int64_t round_words;                                /* 3: words between two rounds' masks */
+} rls_ls_launch;
+typedef struct rls_ls_plan {
+    int32_t err, num_launches;   /* RLS_OK, or what the entry point returns; launches of the whole call (may exceed cap) */
+    char msg[288];
+} rls_ls_plan;
+int rls_maxcut_ls_launch_plan(const rls_graph* g, int32_t what, int64_t B, int32_t ws_bytes, int64_t ws_pitch, int32_t num_spin, int32_t num_draws,
+                              int32_t flags, int64_t scratch_bytes, int32_t cus, rls_ls_launch* out, int32_t cap, rls_ls_plan* info);
 
 /* K10 update_xs_by_vs(xs0, vs0, xs1, vs1, if_maximize)  methods/util_read_data.py:190-202:
  *     rows of (xs1, vs1) that are >= (<= when !if_maximize) replace (xs0, vs0). */

@@ -25,13 +25,13 @@
 #include "rls_cutcount.h"
 #include "rls_sweep.h"
 #include "rls_tile32.h"
+#include "rls_ls_plan.h"
 #include <cstdlib>
 #include <type_traits>
 
 namespace rls {
 
-constexpr int kLsMergeWaves = 4;   // waves that own the top-k merge and the batched sweep; a tile runs on 4 or 8 waves
-constexpr int kTopCap = 16;  // num_spin + 1 <= kTopCap
+// (kLsMergeWaves, kLsRoundWaves, kTopCap: rls_ls_plan.h)
 
 // insert v into the descending list t[0 .. DEPTH) (entries from DEPTH on are untouched: with DEPTH = num_spin + 1 = the
 // rank the threshold is read at, nothing below it can matter)
@@ -617,8 +617,6 @@ __device__ __forceinline__ void ls_ws_pass(const WT* __restrict__ ws, int64_t pi
     }
 }
 
-constexpr int kLsRoundWaves = 8;
-
 // thresh[b] = the (num_spin + 1)-th largest of ws[b, :] + normal(draw) * rd_std  (kthvalue(k = N - num_spin))
 // SD_LDS: rd_std [N] staged in LDS (one broadcast read per quad); false: read from global memory -- rows so long that the
 // 4 N bytes do not fit beside the lists and the stages (N > ~24 900; N % 4 == 0 so that a quad never leaves the array)
@@ -850,406 +848,167 @@ __global__ __launch_bounds__(W * kWave) void k_ls_apply_rounds32(uint8_t* __rest
     else tile32_store_bytes<false>(x, B, N, b0, words32, lane, w, W, ch_env, stage);
 }
 
-static size_t ls_apply32_lds(int64_t N, int W, bool stage = false) {
-    return (((size_t)N * 4 + 15) & ~(size_t)15) + (size_t)W * kWave * 8 + (stage ? (size_t)W * kStageBytes : 0);
-}
-
-static size_t ls_apply_lds(int64_t N, int W, bool stage) {
-    return (size_t)((N + 1) & ~1ll) * 8 + (size_t)W * kWave * 8 + (stage ? (size_t)W * kStageBytes : 0);
-}
-// N beyond the proposal kernel's tile + stages but within the bare tile (15 500 < N <= 20 224): mask kernels + the 4-wave apply kernel
-// (rows of 16- or 8-byte multiples take half tiles there instead: their loader keeps 64-byte runs, the bare tile's reads 16 B per env)
-static bool ls_big_tile(int64_t N) {
-    return (size_t)((N + 1) & ~1ll) * 8 + (size_t)kLsRoundWaves * kWave * 8 + (size_t)kLsRoundWaves * kStageBytes > (size_t)kLdsBytes &&
-           ls_apply_lds(N, 4, false) <= (size_t)kLdsBytes && (N & 7) != 0;
-}
-// N past the 64-env tile altogether but within the half tile (20 224 < N <= ~39 900): mask kernels + the apply kernel on half tiles
-static bool ls_half_tile(int64_t N) {
-    return !ls_big_tile(N) && ls_apply32_lds(N, kLsRoundWaves) <= (size_t)kLdsBytes &&
-           (size_t)((N + 1) & ~1ll) * 8 + (size_t)kLsRoundWaves * kWave * 8 + (size_t)kLsRoundWaves * kStageBytes > (size_t)kLdsBytes;
-}
-static bool ls_sd_global() {   // dev knob: rd_std read from global memory even where it fits LDS
-    const bool on = knob_on(KN_LS_SD_GLOBAL);
-    return on;
-}
-// workgroups per tile for the noise passes: 1 once the tiles alone fill the chip, else up to 8 slices of the rows
-static int ls_slices(int64_t B, int64_t nchunks) {
-    const int force = (int)knob(KN_LS_SLICES, 0);   // dev knob
-    const int64_t tiles = ceil_div(B, kWave);
-    int S = force > 0 ? force : (int)(num_cus() / (tiles > 0 ? tiles : 1));
-    if (S > 8) S = 8;
-    if ((int64_t)S * 2 * kLsRoundWaves > nchunks) S = (int)(nchunks / (2 * kLsRoundWaves));   // a slice keeps every wave busy
-    return S < 1 ? 1 : S;
-}
-constexpr size_t kLsMaxMaskBytes = (size_t)1 << 30;   // all rounds' mask words at once only while they stay under 1 GiB
-static size_t ls_scratch_bytes(int64_t B, int64_t N, int S, int rounds = 1) {   // rounds: mask words of that many rounds at once
-    const size_t tiles = (size_t)ceil_div(B, kWave);
-    const size_t lists = S > 1 ? tiles * S * kTopCap * kWave * 4 : 0;
-    const size_t all = tiles * (size_t)N * 8 * (size_t)(rounds > 1 ? rounds : 1);
-    // one round's words when the noise pass is split (S > 1); every round's whenever more than one is asked for and they fit
-    const size_t masks = rounds > 1 ? (all <= kLsMaxMaskBytes ? all : (S > 1 ? tiles * (size_t)N * 8 : 0)) : (S > 1 ? all : 0);
-    return lists > masks ? lists : masks;
-}
-// (rd_std always fits LDS beside the stages here: 4 N bytes, N bounded by the proposal kernel's tile)
-// rd_std beside the stages (sd_lds), or read from global memory where 4 N bytes do not fit (needs N % 4 == 0)
-// (the lane = node mask kernel keeps nothing in LDS: rd_std in registers, ws read as it lies)
-static size_t ls_mask_lds(int64_t, bool = true) { return 0; }
-static size_t ls_threshold_lds(int64_t N, bool sd_lds = true) {
-    return (size_t)kLsRoundWaves * kTopCap * kWave * 4 + (size_t)kLsRoundWaves * kStageBytes + (sd_lds ? (size_t)((N + 3) & ~3ll) * 4 : 0);
-}
-static bool ls_noise_sd_lds(int64_t N) { return ls_threshold_lds(N, true) <= (size_t)kLdsBytes; }   // (the threshold kernel is the larger)
-static bool ls_noise_passes_fit(int64_t N) { return ls_noise_sd_lds(N) || (N & 3) == 0; }
-static size_t ls_propose_lds(int64_t N, bool sd_lds) {
-    return (size_t)((N + 1) & ~1ll) * 8 + (size_t)kLsRoundWaves * kWave * 8 + (size_t)kLsRoundWaves * kStageBytes +
-           (sd_lds ? (size_t)((N + 3) & ~3ll) * 4 : 0);
-}
-// N past the half tile too, within the narrow tiles (rls_tile32.h: 16 / 8 envs per workgroup; ~39 900 < N <= ~155 000): mask kernels,
-// then every round's proposal through K6 on narrow tiles with the mask words as its bit-packed mask (round 5; such graphs ran the
-// search as torch ops on [B, N] float tensors around K6: 16.6 ms for 4096 envs at N = 44 000)
-static bool ls_narrow_tile(int64_t N) {
-    return !ls_big_tile(N) && !ls_half_tile(N) && ls_propose_lds(N, false) > (size_t)kLdsBytes &&
-           (((size_t)(N + 2) + 15) & ~(size_t)15) + (size_t)8 * kWave * 8 <= (size_t)kLdsBytes && knob(KN_NARROW_TILE, 1) != 0;
-}
-
 }  // namespace rls
-
 using namespace rls;
 
-
-// LDS bytes of the W-wave layout (W = 4: compact, the sweep offsets reuse the proposal tile; W = 8: separate tables)
-static size_t ls_lds_bytes(int64_t N, int W) {
-    const size_t sd_bytes = (size_t)((N + 3) & ~3ll) * 4;   // rd_std in LDS (W = 8; the compact layout keeps it in the proposal tile)
-#ifdef RLS_LS_ROUND_LANE_ENV
-    const size_t sd4 = sd_bytes;
-#else
-    const size_t sd4 = 0;
-#endif
-    return W == kLsMergeWaves
-               ? sd4 + (size_t)(N + 2) * 8 + (size_t)N * 8 + (size_t)kRing * 4 + (size_t)W * kWave * 8
-               : sd_bytes + (size_t)(N + 2) * 8 + (size_t)N * 8 + (size_t)kRing * 4 + (size_t)W * kWave * 8 +
-                     (size_t)kLsMergeWaves * kTopCap * kWave * 4;
+// ---- host side: every launcher validates, asks rls_ls_plan.h for the launches, and makes them ----
+static_assert(kPlanStageBytes == kStageBytes && kPlanHalf == kHalf && kPlanRing == kRing && kPlanRingMaxRun == kRingMaxRun, "rls_ls_plan.h and the kernels' headers agree");
+static int refuse(const LsPlan& p) { return fail(p.err, "%s", p.msg); }
+template <typename... KA, typename... A>
+static int launch(void (*kern)(KA...), const char* name, const LsLaunch& l, void* stream, A... args) {
+    ensure_dyn_lds((const void*)kern, (size_t)l.lds);
+    hipLaunchKernelGGL(kern, dim3(l.grid[0], l.grid[1], l.grid[2]), dim3(l.block), (size_t)l.lds, as_stream(stream), static_cast<KA>(args)...);
+    return check_launch(name);
+}
+// the weights' entry type (ws_bytes = 1 | 2) as a type
+template <typename F> static int with_ws(int ws_bytes, F&& f) { return ws_bytes == 1 ? f(int8_t{}) : f(int16_t{}); }
+// the shape the planner sees (pointers only tested for NULL and alignment; ws_pitch = 0 means N).  False: nothing to plan for.
+static bool ls_shape(LsShape* out, const rls_graph* g, int64_t B, int32_t ws_bytes, int32_t num_spin, int32_t num_draws, const void* x = nullptr,
+                     const void* noise = nullptr, const void* ws = nullptr, int64_t ws_pitch = 0, const void* scratch = nullptr, int64_t scratch_bytes = 0, int cus = 0) {
+    if (!g || g->num_nodes <= 0 || B <= 0 || (ws_bytes != 1 && ws_bytes != 2)) return false;
+    LsShape& s = *out;
+    s.N = g->num_nodes; s.B = B; s.E = g->num_stored_edges; s.G = g->num_sweep_groups; s.ws_pitch = ws_pitch == 0 ? s.N : ws_pitch;
+    s.ws_bytes = ws_bytes; s.num_spin = num_spin; s.num_draws = num_draws; s.max_degree = g->max_degree; s.cus = cus > 0 ? cus : num_cus();
+    s.weighted = g->wgt != nullptr; s.has_levels = g->sweep_lv_ptr && g->sweep_lv_data; s.has_batches = g->sweep_rowptr && g->sweep_stream;
+    s.x_aligned = tile_rows_aligned(x, s.N, 1); s.noise16 = (((uintptr_t)noise) & 15) == 0;
+    // ws rows start ws_pitch ENTRIES apart: any N works once the pitch is a multiple of 16 bytes
+    s.pitch_ok = s.ws_pitch >= s.N && ((s.ws_pitch * ws_bytes) & 15) == 0 && (((uintptr_t)ws) & 15) == 0;
+    s.scratch_ok = scratch && (((uintptr_t)scratch) & 15) == 0; s.scratch_bytes = scratch_bytes > 0 ? (size_t)scratch_bytes : 0;
+    return true;
 }
 
-// Waves per tile.  What counts is waves per SIMD (the VALU issues a wave's stream at ~5 cycles per instruction and two or more
-// waves' at ~2.6: tools/ceilings/valu_issue.hip): 8 waves when a CU holds one tile anyway -- at most one tile per CU in the launch, or
-// rows so long that two 4-wave layouts do not fit LDS (N > ~3100) -- else 4 waves and two tiles per CU.  Measured
-// (tools/timing/ls_waves.py): G22-sized 2^14 envs 0.53 -> 0.46 ms with 8, 2^15 0.83 -> 0.72 with 4; G(5000, 20000) 2^16 4.02 -> 3.13
-// with 8.  0 = neither layout fits.
-static int ls_pick_waves(int64_t N, int64_t B) {
-    const int force_w = (int)knob(KN_LS_WAVES, 0);   // dev knob
-    // (which graphs the fused kernel takes, and from where two 4-wave tiles share a CU, is decided on the layout WITH rd_std's own
-    // 4N bytes, as until round 6: the compact layout now keeps rd_std inside the proposal tile and launches with less, but the
-    // rows that gains -- N ~ 6500 .. 9000, one tile per CU -- are rows the round kernels win on (envs/env_L2A.py))
-    const size_t sd = (size_t)((N + 3) & ~3ll) * 4;
-    auto fit = [&](int w) { return ls_lds_bytes(N, w) + (w == kLsMergeWaves ? sd : 0); };
-    const bool two_small = 2 * fit(4) <= (size_t)kLdsBytes;
-    int W = force_w == 4 || force_w == 8 ? force_w : (ceil_div(B, kWave) <= (int64_t)num_cus() || !two_small ? 8 : 4);
-    if (W == 8 && fit(8) > (size_t)kLdsBytes) W = 4;
-    return fit(W) <= (size_t)kLdsBytes ? W : 0;
-}
-
-// ws rows start ws_pitch ENTRIES apart (0 = N): any N works once the pitch is a multiple of 16 bytes
-static bool ls_pitch_ok(const void* ws, int64_t pitch, int32_t ws_bytes, int64_t N) {
-    return pitch >= N && ((pitch * ws_bytes) & 15) == 0 && (((uintptr_t)ws) & 15) == 0;
-}
-
+// The four host queries: views of the planner.  1 when rls_maxcut_local_search covers this graph / batch / num_spin; 1 when
+// rls_maxcut_ls_threshold / _ls_propose / _ls_rounds do (a tile that fits LDS -- the bare 64-env tile, the half and the narrow tiles
+// need the scratch buffer: the rounds run through the mask words there); the bytes of caller-provided scratch with which they split a
+// tile's noise pass over several workgroups (0: the batch alone fills the chip, or the rows are too short to split; without it
+// they run one workgroup per tile); and over how many (1: the tiles fill the chip by themselves)
 extern "C" int rls_maxcut_local_search_supported(const rls_graph* g, int64_t B, int32_t num_spin) {
-    if (!g || g->num_nodes <= 0) return 0;
-    const int64_t N = g->num_nodes;
-    if (num_spin < 0 || num_spin + 1 > kTopCap || num_spin >= N) return 0;
-    if (g->wgt || g->max_degree >= kRingMaxRun) return 0;
-    if (pick_planes(g->num_stored_edges) == 0) return 0;
-    if ((N & 3) != 0) return 0;   // rows that are not dword-aligned: the round kernels (any N, and faster there than an element-wise fused form was)
-    return ls_pick_waves(N, B > 0 ? B : 1) != 0;
+    LsShape s; return ls_shape(&s, g, B > 0 ? B : 1, 1, num_spin, 1) && ls_fused_supported(s);
+}
+extern "C" int rls_maxcut_ls_rounds_supported(const rls_graph* g, int32_t num_spin) {
+    LsShape s; return ls_shape(&s, g, 1, 1, num_spin, 1) && ls_rounds_supported(s);
+}
+extern "C" int64_t rls_maxcut_ls_scratch_bytes(const rls_graph* g, int64_t B, int32_t ws_bytes, int32_t num_draws) {
+    LsShape s; return ls_shape(&s, g, B, ws_bytes, 0, num_draws) ? (int64_t)ls_scratch_bytes(s) : 0;
+}
+extern "C" int rls_maxcut_ls_slices(const rls_graph* g, int64_t B, int32_t ws_bytes) {
+    LsShape s; return ls_shape(&s, g, B, ws_bytes, 0, 1) ? ls_tile(s).slices : 1;
+}
+// the launches an entry point would make (include/rlsolver_hip.h): the launchers' own planner on a shape given by values
+extern "C" int rls_maxcut_ls_launch_plan(const rls_graph* g, int32_t what, int64_t B, int32_t ws_bytes, int64_t ws_pitch, int32_t num_spin, int32_t num_draws,
+                                         int32_t flags, int64_t scratch_bytes, int32_t cus, rls_ls_launch* out, int32_t cap, rls_ls_plan* info) {
+    auto base = [&](int flag) { return reinterpret_cast<const void*>((uintptr_t)(flags & flag ? 4 : 16)); };      // (an address of that alignment)
+    LsShape s;
+    RLS_REQUIRE(what >= RLS_LS_PLAN_FUSED && what <= RLS_LS_PLAN_ROUNDS && ws_pitch >= 0 && num_draws >= 1 && info && cap >= 0 && (out || cap == 0) &&
+                    ls_shape(&s, g, B, ws_bytes, num_spin, num_draws, base(RLS_LS_PLAN_X_UNALIGNED), base(RLS_LS_PLAN_NOISE_UNALIGNED), base(0), ws_pitch,
+                             flags & RLS_LS_PLAN_NO_SCRATCH ? nullptr : base(RLS_LS_PLAN_SCRATCH_UNALIGNED), scratch_bytes, cus), RLS_EINVAL, "bad arguments");
+    const LsPlan p = what == RLS_LS_PLAN_FUSED ? plan_ls_fused(s) : what == RLS_LS_PLAN_THRESHOLD ? plan_ls_threshold(s)
+                     : what == RLS_LS_PLAN_PROPOSE ? plan_ls_propose(s) : plan_ls_rounds(s);
+    *info = rls_ls_plan{};
+    info->err = p.err;
+    snprintf(info->msg, sizeof(info->msg), "%s", p.msg);
+    for (int r = 0; r < p.repeat; ++r)
+        for (int i = 0; i < p.n; ++i)
+            for (int k = 0; k < (p.l[i].kernel == LSK_K6 ? p.l[i].rounds : 1); ++k, ++info->num_launches)      // (a K6 call per round)
+                if (info->num_launches < cap) { out[info->num_launches] = p.l[i]; out[info->num_launches].first_round = r * p.per_launch + k; }
+    return RLS_OK;
 }
 
-extern "C" int rls_maxcut_local_search(const rls_graph* g, uint8_t* x, int64_t B, const void* ws, int32_t ws_bytes, int64_t ws_pitch,
-                                       const float* rd_std, const float* noise, uint64_t seed, int64_t env_offset,
-                                       int32_t num_iters, int32_t num_spin, int32_t first_draw_proposes, int64_t* obj,
-                                       int32_t compute_obj, void* stream) {
+extern "C" int rls_maxcut_local_search(const rls_graph* g, uint8_t* x, int64_t B, const void* ws, int32_t ws_bytes, int64_t ws_pitch, const float* rd_std,
+                                       const float* noise, uint64_t seed, int64_t env_offset, int32_t num_iters, int32_t num_spin, int32_t first_draw_proposes,
+                                       int64_t* obj, int32_t compute_obj, void* stream) {
     if (int rc = check_graph(g)) return rc;
     RLS_REQUIRE(B >= 0 && num_iters >= 0, RLS_EINVAL, "bad sizes");
     if (B == 0) return RLS_OK;
     RLS_REQUIRE(x && ws && rd_std && obj, RLS_EINVAL, "NULL pointer");
-    RLS_REQUIRE(ws_bytes == 1 || ws_bytes == 2, RLS_EINVAL, "ws_bytes must be 1 or 2 (rls_maxcut_ls_weights writes either)");
-    const int64_t N = g->num_nodes, E = g->num_stored_edges;
-    RLS_REQUIRE(num_spin >= 0 && num_spin + 1 <= kTopCap && num_spin < N, RLS_EUNSUPPORTED,
-                "num_spin=%d outside [0, %d] (and < N)", num_spin, kTopCap - 1);
-    RLS_REQUIRE(!g->wgt && g->max_degree < kRingMaxRun, RLS_EUNSUPPORTED,
-                "fused local search needs an unweighted graph with max degree < %d", kRingMaxRun);
-    // x and noise: rows that start 4-byte aligned on 16-byte bases (N % 4 == 0).  ws is read in 16-byte pieces, the last piece
-    // of a row included: its rows sit ws_pitch entries apart, a multiple of 16 bytes (rls_maxcut_ls_weights writes that layout),
-    // so no piece leaves its row -- an exactly sized [B, N] array whose rows are not 16-byte multiples is refused, not over-read
-    if (ws_pitch == 0) ws_pitch = N;
-    RLS_REQUIRE(ls_pitch_ok(ws, ws_pitch, ws_bytes, N), RLS_EUNSUPPORTED,
-                "fused local search reads ws in 16-byte pieces: rows must sit a multiple of 16 bytes apart on a 16-byte base "
-                "(ws_pitch=%lld entries of %d bytes, N=%lld)", (long long)ws_pitch, (int)ws_bytes, (long long)N);
-    const bool aligned = tile_rows_aligned(x, N, 1) && (((uintptr_t)noise) & 15) == 0;
-    RLS_REQUIRE(aligned, RLS_EUNSUPPORTED, "fused local search needs rows of x and noise that start 4-byte aligned on 16-byte bases "
-                "(N=%lld): rls_maxcut_ls_threshold / rls_maxcut_ls_rounds take any layout", (long long)N);
-    int W = ls_pick_waves(N, B);
-    RLS_REQUIRE(W != 0, RLS_EUNSUPPORTED, "N=%lld needs %zu B of LDS (max %d)", (long long)N, ls_lds_bytes(N, 4), kLdsBytes);
-    const size_t lds = ls_lds_bytes(N, W);
-    const int P = pick_planes(E);
-    RLS_REQUIRE(P != 0, RLS_EUNSUPPORTED, "E'=%lld too large", (long long)E);
-    const dim3 grid((unsigned)ceil_div(B, kWave)), block(W * kWave);
-    hipStream_t s = as_stream(stream);
-    const int halve = g->if_bidirectional ? 1 : 0;
-    const bool no_levels = knob_on(KN_SWEEP_NO_LEVELS);   // dev knob
-    const bool levels = !no_levels && g->sweep_lv_ptr && g->sweep_lv_data && g->num_sweep_groups > 0 &&
-                        g->num_sweep_groups <= N;
-    const int batched = levels ? 2 : (g->sweep_rowptr != nullptr && g->sweep_stream != nullptr ? 1 : 0);
+    LsShape s;
+    RLS_REQUIRE(ls_shape(&s, g, B, ws_bytes, num_spin, 1, x, noise, ws, ws_pitch), RLS_EINVAL, "ws_bytes must be 1 or 2 (rls_maxcut_ls_weights writes either)");
+    const LsPlan p = plan_ls_fused(s);
+    if (p.err) return refuse(p);
+    const LsLaunch& l = p.l[0];
     // sweep schedule: level groups (lane = node) | level schedule stream (lane = env) | the CSR as it is
-    const int32_t* rp_src = batched == 2 ? g->sweep_lv_ptr : (batched ? g->sweep_rowptr : g->rowptr);
-    const int32_t* sw_src = batched == 2 ? g->sweep_lv_data : (batched ? g->sweep_stream : g->col);
-    const int64_t sw_len = batched == 2 ? g->num_sweep_groups : (batched ? g->nnz + N : g->nnz);
-#define LAUNCH_LSF(AL, WT, PP)                                                                                       \
-    do {                                                                                                             \
-        auto kern = W == 8 ? k_maxcut_local_search<AL, WT, PP, 8> : k_maxcut_local_search<AL, WT, PP, 4>;             \
-        if (lds > 64 * 1024)                                                                                         \
-            ensure_dyn_lds((const void*)kern, lds);      \
-        hipLaunchKernelGGL(kern, grid, block, lds, s, x, B, N, g->eu, g->ev, E, halve, rp_src, sw_src, sw_len,        \
-                           (const WT*)ws, ws_pitch, rd_std, noise, seed, env_offset, (int)num_iters, (int)num_spin,   \
-                           (int)first_draw_proposes, obj, (int)compute_obj, batched);                                 \
-    } while (0)
-    // two counter widths (the 12- and 20-plane forms of the edge counter save a few carry steps per 1024 edges: not worth
-    // a second pair of 190 KB kernels each); rows that are not 16-byte multiples always take the 4-wave layout
-#define DISPATCH_P(AL, WT)                        \
-    switch (P) {                                  \
-        case 12:                                  \
-        case 16: LAUNCH_LSF(AL, WT, 16); break;   \
-        default: LAUNCH_LSF(AL, WT, 24); break;   \
-    }
-    // (an element-wise form for rows that are not dword-aligned existed until round 3: 180 - 300 KB per instantiation, and slower
-    // there than the round kernels, which read the weights on a padded pitch)
-    if (ws_bytes == 1) { DISPATCH_P(true, int8_t) } else { DISPATCH_P(true, int16_t) }
-#undef DISPATCH_P
-#undef LAUNCH_LSF
-    return check_launch("k_maxcut_local_search");
+    const int32_t* rp_src = l.batched == 2 ? g->sweep_lv_ptr : (l.batched ? g->sweep_rowptr : g->rowptr);
+    const int32_t* sw_src = l.batched == 2 ? g->sweep_lv_data : (l.batched ? g->sweep_stream : g->col);
+    const int64_t sw_len = l.batched == 2 ? g->num_sweep_groups : (l.batched ? g->nnz + s.N : g->nnz);
+    return with_ws(ws_bytes, [&](auto wt) { return with_value<16, 24>(l.planes, [&](auto P) { return with_value<8, 4>(l.waves, [&](auto W) {
+        return launch(k_maxcut_local_search<true, decltype(wt), P(), W()>, "k_maxcut_local_search", l, stream, x, B, s.N, g->eu, g->ev, s.E, g->if_bidirectional ? 1 : 0,
+                      rp_src, sw_src, sw_len, ws, s.ws_pitch, rd_std, noise, seed, env_offset, num_iters, num_spin, first_draw_proposes, obj, compute_obj, l.batched); }); }); });
 }
 
-// 1 when rls_maxcut_ls_threshold / rls_maxcut_ls_propose cover this graph (a tile that fits LDS; ws rows on a 16-byte pitch)
-extern "C" int rls_maxcut_ls_rounds_supported(const rls_graph* g, int32_t num_spin) {
-    if (!g || g->num_nodes <= 0) return 0;
-    const int64_t N = g->num_nodes;
-    if (num_spin < 0 || num_spin + 1 > kTopCap || num_spin >= N) return 0;
-    if (pick_planes(g->num_stored_edges) == 0) return 0;
-    // (the bare 64-env tile and the half tile need the scratch buffer: the rounds run through the mask words there)
-    return ls_propose_lds(N, false) <= (size_t)kLdsBytes || ((ls_big_tile(N) || ls_half_tile(N) || ls_narrow_tile(N)) && ls_noise_passes_fit(N));
-}
-
-// bytes of caller-provided scratch with which the two entry points below split a tile's noise pass over several workgroups
-// (0: the batch alone fills the chip, or the rows are too short to split); without it they run one workgroup per tile
-extern "C" int64_t rls_maxcut_ls_scratch_bytes(const rls_graph* g, int64_t B, int32_t ws_bytes, int32_t num_draws) {
-    if (!g || g->num_nodes <= 0 || B <= 0 || (ws_bytes != 1 && ws_bytes != 2)) return 0;
-    const int64_t N = g->num_nodes;
-    const int64_t nch = ws_bytes == 1 ? ls_num_chunks<int8_t>(N) : ls_num_chunks<int16_t>(N);
-    const size_t need = ls_scratch_bytes(B, N, ls_slices(B, nch), num_draws);
-    if (ls_big_tile(N) || ls_half_tile(N) || ls_narrow_tile(N)) {   // the mask words are how the rounds run at all here: at least one round's
-        const size_t one = (size_t)ceil_div(B, kWave) * (size_t)N * 8;
-        return (int64_t)(need > one ? need : one);
-    }
-    return (int64_t)need;
-}
-
-// workgroups per tile the noise passes of a batch of B envs are split over when the scratch buffer is there (1: the tiles fill
-// the chip by themselves)
-extern "C" int rls_maxcut_ls_slices(const rls_graph* g, int64_t B, int32_t ws_bytes) {
-    if (!g || g->num_nodes <= 0 || B <= 0 || (ws_bytes != 1 && ws_bytes != 2)) return 1;
-    return ls_slices(B, ws_bytes == 1 ? ls_num_chunks<int8_t>(g->num_nodes) : ls_num_chunks<int16_t>(g->num_nodes));
-}
-
-
-extern "C" int rls_maxcut_ls_threshold(const rls_graph* g, int64_t B, const void* ws, int32_t ws_bytes, int64_t ws_pitch,
-                                       const float* rd_std, uint64_t seed, int64_t env_offset, int32_t draw, int32_t num_spin,
-                                       float* thresh, void* scratch, int64_t scratch_bytes, void* stream) {
+extern "C" int rls_maxcut_ls_threshold(const rls_graph* g, int64_t B, const void* ws, int32_t ws_bytes, int64_t ws_pitch, const float* rd_std, uint64_t seed,
+                                       int64_t env_offset, int32_t draw, int32_t num_spin, float* thresh, void* scratch, int64_t scratch_bytes, void* stream) {
     if (int rc = check_graph(g)) return rc;
     RLS_REQUIRE(B >= 0 && draw >= 0, RLS_EINVAL, "bad sizes");
     if (B == 0) return RLS_OK;
     RLS_REQUIRE(ws && rd_std && thresh, RLS_EINVAL, "NULL pointer");
-    RLS_REQUIRE(ws_bytes == 1 || ws_bytes == 2, RLS_EINVAL, "ws_bytes must be 1 or 2 (rls_maxcut_ls_weights writes either)");
-    const int64_t N = g->num_nodes;
-    RLS_REQUIRE(num_spin >= 0 && num_spin + 1 <= kTopCap && num_spin < N, RLS_EUNSUPPORTED, "num_spin=%d outside [0, %d] (and < N)",
-                num_spin, kTopCap - 1);
-    if (ws_pitch == 0) ws_pitch = N;
-    RLS_REQUIRE(ls_pitch_ok(ws, ws_pitch, ws_bytes, N), RLS_EUNSUPPORTED,
-                "ws rows must start 16-byte aligned: pitch %lld entries of %d bytes (N=%lld)", (long long)ws_pitch, (int)ws_bytes, (long long)N);
-    const bool sd_lds = ls_noise_sd_lds(N);
-    RLS_REQUIRE(ls_noise_passes_fit(N), RLS_EUNSUPPORTED, "N=%lld: rd_std does not fit LDS and N is not a multiple of 4", (long long)N);
-    const size_t lds = ls_threshold_lds(N, sd_lds);
-    int S = ls_slices(B, ws_bytes == 1 ? ls_num_chunks<int8_t>(N) : ls_num_chunks<int16_t>(N));
-    if (!scratch || (size_t)scratch_bytes < ls_scratch_bytes(B, N, S) || (((uintptr_t)scratch) & 15) != 0) S = 1;
-    const dim3 grid((unsigned)ceil_div(B, kWave), (unsigned)S), block(kLsRoundWaves * kWave);
-    hipStream_t s = as_stream(stream);
-#define LAUNCH_TH(WT)                                                                                                  \
-    do {                                                                                                               \
-        auto kern = sd_lds ? k_ls_threshold<WT, true> : k_ls_threshold<WT, false>;                                     \
-        if (lds > 64 * 1024) ensure_dyn_lds((const void*)kern, lds); \
-        hipLaunchKernelGGL(kern, grid, block, lds, s, (const WT*)ws, ws_pitch, B, N, rd_std, seed, env_offset, (int)draw, (int)num_spin, thresh, \
-                           (float*)scratch);                                                                           \
-    } while (0)
-    if (ws_bytes == 1) LAUNCH_TH(int8_t); else LAUNCH_TH(int16_t);
-#undef LAUNCH_TH
-    if (int rc = check_launch("k_ls_threshold")) return rc;
-    if (S > 1) {
-        hipLaunchKernelGGL(k_ls_threshold_merge, dim3(grid.x), dim3(kWave), 0, s, (const float*)scratch, S, B, (int)num_spin, thresh);
-        return check_launch("k_ls_threshold_merge");
-    }
+    LsShape s;
+    RLS_REQUIRE(ls_shape(&s, g, B, ws_bytes, num_spin, 1, nullptr, nullptr, ws, ws_pitch, scratch, scratch_bytes), RLS_EINVAL,
+                "ws_bytes must be 1 or 2 (rls_maxcut_ls_weights writes either)");
+    const LsPlan p = plan_ls_threshold(s);
+    if (p.err) return refuse(p);
+    if (int rc = with_ws(ws_bytes, [&](auto wt) { return with_bool(p.l[0].sd_lds != 0, [&](auto SD) {
+            return launch(k_ls_threshold<decltype(wt), SD()>, "k_ls_threshold", p.l[0], stream, ws, s.ws_pitch, B, s.N, rd_std, seed, env_offset, draw, num_spin, thresh, scratch); }); }))
+        return rc;
+    return p.n == 1 ? RLS_OK : launch(k_ls_threshold_merge, "k_ls_threshold_merge", p.l[1], stream, scratch, p.l[1].rounds, B, num_spin, thresh);
+}
+// a rounds plan from draw `first_draw` on: every launch of it, in order
+static int ls_run_rounds(const LsPlan& p, const rls_graph* g, const LsShape& s, uint8_t* x, const void* ws, const float* rd_std, const float* thresh, uint64_t seed,
+                         int64_t env_offset, int32_t first_draw, int64_t* obj, void* scratch, void* stream) {
+    if (p.err) return refuse(p);
+    const int64_t B = s.B, N = s.N, E = s.E, tiles = ceil_div(B, kWave);
+    const int halve = g->if_bidirectional ? 1 : 0;
+    auto run = [&](const LsLaunch& l, int draw) {
+        switch (l.kernel) {
+            case LSK_MASK:
+                return with_ws(l.ws_bytes, [&](auto wt) { return with_bool(l.sd_lds != 0, [&](auto SD) {
+                    return launch(k_ls_mask<decltype(wt), SD()>, "k_ls_mask", l, stream, ws, s.ws_pitch, B, N, rd_std, thresh, seed, env_offset, draw, scratch, l.round_words); }); });
+            case LSK_PROPOSE:
+                if (l.premask)
+                    return launch(k_ls_propose<int8_t, 24, false, true>, "k_ls_propose", l, stream, x, B, N, g->eu, g->ev, E, halve, ws, s.ws_pitch, rd_std, thresh, seed,
+                                  env_offset, draw, obj, scratch, l.x_aligned);
+                return with_ws(l.ws_bytes, [&](auto wt) { return with_bool(l.sd_lds != 0, [&](auto SD) {
+                    return launch(k_ls_propose<decltype(wt), 24, SD(), false>, "k_ls_propose", l, stream, x, B, N, g->eu, g->ev, E, halve, ws, s.ws_pitch, rd_std, thresh, seed,
+                                  env_offset, draw, obj, scratch, l.x_aligned); }); });
+            case LSK_APPLY32:
+                return launch(k_ls_apply_rounds32<24, kLsRoundWaves>, "k_ls_apply_rounds", l, stream, x, B, N, g->eu, g->ev, E, halve, scratch, tiles, l.rounds, obj, l.x_aligned, l.stage);
+            case LSK_APPLY:
+                return with_value<4, kLsRoundWaves>(l.waves, [&](auto W) {
+                    return launch(k_ls_apply_rounds<24, W()>, "k_ls_apply_rounds", l, stream, x, B, N, g->eu, g->ev, E, halve, scratch, l.rounds, obj, l.x_aligned, l.stage); });
+            default:   // LSK_K6: every round's mask words as K6's bit-packed mask
+                for (int r = 0; r < l.rounds; ++r)
+                    if (int rc = rls_maxcut_propose_accept(g, x, B, (const uint64_t*)scratch + (size_t)r * (size_t)tiles * (size_t)N, 1, obj, stream)) return rc;
+                return (int)RLS_OK;
+        }
+    };
+    for (int r = 0; r < p.repeat; ++r)
+        for (int i = 0; i < p.n; ++i)
+            if (int rc = run(p.l[i], first_draw + r * p.per_launch)) return rc;
     return RLS_OK;
 }
 
-extern "C" int rls_maxcut_ls_rounds(const rls_graph* g, uint8_t* x, int64_t B, const void* ws, int32_t ws_bytes, int64_t ws_pitch,
-                                    const float* rd_std, const float* thresh, uint64_t seed, int64_t env_offset, int32_t first_draw,
-                                    int32_t num_draws, int64_t* obj, void* scratch, int64_t scratch_bytes, void* stream);
-
-extern "C" int rls_maxcut_ls_propose(const rls_graph* g, uint8_t* x, int64_t B, const void* ws, int32_t ws_bytes, int64_t ws_pitch,
-                                     const float* rd_std, const float* thresh, uint64_t seed, int64_t env_offset, int32_t draw,
-                                     int64_t* obj, void* scratch, int64_t scratch_bytes, void* stream) {
+extern "C" int rls_maxcut_ls_propose(const rls_graph* g, uint8_t* x, int64_t B, const void* ws, int32_t ws_bytes, int64_t ws_pitch, const float* rd_std, const float* thresh,
+                                     uint64_t seed, int64_t env_offset, int32_t draw, int64_t* obj, void* scratch, int64_t scratch_bytes, void* stream) {
     if (int rc = check_graph(g)) return rc;
     RLS_REQUIRE(B >= 0 && draw >= 0, RLS_EINVAL, "bad sizes");
     if (B == 0) return RLS_OK;
     RLS_REQUIRE(x && ws && rd_std && thresh && obj, RLS_EINVAL, "NULL pointer");
-    RLS_REQUIRE(ws_bytes == 1 || ws_bytes == 2, RLS_EINVAL, "ws_bytes must be 1 or 2 (rls_maxcut_ls_weights writes either)");
-    const int64_t N = g->num_nodes, E = g->num_stored_edges;
-    if (ws_pitch == 0) ws_pitch = N;
-    RLS_REQUIRE(ls_pitch_ok(ws, ws_pitch, ws_bytes, N), RLS_EUNSUPPORTED,
-                "ws rows must start 16-byte aligned: pitch %lld entries of %d bytes (N=%lld)", (long long)ws_pitch, (int)ws_bytes, (long long)N);
-    const int x_aligned = tile_rows_aligned(x, N, 1) ? 1 : 0;   // else the funnel-shift form of the row-piece stage
-    if (ls_propose_lds(N, false) > (size_t)kLdsBytes && (ls_big_tile(N) || ls_half_tile(N) || ls_narrow_tile(N)))   // mask kernel + the apply kernel (needs the scratch)
-        return rls_maxcut_ls_rounds(g, x, B, ws, ws_bytes, ws_pitch, rd_std, thresh, seed, env_offset, draw, 1, obj, scratch, scratch_bytes, stream);
-    RLS_REQUIRE(ls_propose_lds(N, false) <= (size_t)kLdsBytes, RLS_EUNSUPPORTED, "N=%lld needs %zu B of LDS (max %d)", (long long)N,
-                ls_propose_lds(N, false), kLdsBytes);
-    const int P = pick_planes(E);
-    RLS_REQUIRE(P != 0, RLS_EUNSUPPORTED, "E'=%lld too large", (long long)E);
-    int S = ls_slices(B, ws_bytes == 1 ? ls_num_chunks<int8_t>(N) : ls_num_chunks<int16_t>(N));
-    if (!scratch || (size_t)scratch_bytes < ls_scratch_bytes(B, N, S) || (((uintptr_t)scratch) & 15) != 0) S = 1;
-    const dim3 grid((unsigned)ceil_div(B, kWave)), block(kLsRoundWaves * kWave);
-    hipStream_t s = as_stream(stream);
-    const int halve = g->if_bidirectional ? 1 : 0;
-    if (S > 1) {   // the mask words first, S workgroups per tile
-        const size_t ldm = ls_mask_lds(N);
-        const dim3 gm(grid.x, (unsigned)S);
-#define LAUNCH_MK(WT)                                                                                                  \
-    do {                                                                                                               \
-        auto kern = k_ls_mask<WT>;                                                                                     \
-        if (ldm > 64 * 1024) ensure_dyn_lds((const void*)kern, ldm); \
-        hipLaunchKernelGGL(kern, gm, block, ldm, s, (const WT*)ws, ws_pitch, B, N, rd_std, thresh, seed, env_offset, (int)draw, (uint64_t*)scratch, (int64_t)0); \
-    } while (0)
-        if (ws_bytes == 1) LAUNCH_MK(int8_t); else LAUNCH_MK(int16_t);
-#undef LAUNCH_MK
-        if (int rc = check_launch("k_ls_mask")) return rc;
-    }
-    const bool sd_lds = S == 1 && !ls_sd_global() && ls_propose_lds(N, true) <= (size_t)kLdsBytes;
-    const size_t lds = ls_propose_lds(N, sd_lds);
-#define LAUNCH_PR(WT, PP, SD, PM)                                                                                      \
-    do {                                                                                                               \
-        auto kern = k_ls_propose<WT, PP, SD, PM>;                                                                      \
-        if (lds > 64 * 1024) ensure_dyn_lds((const void*)kern, lds); \
-        hipLaunchKernelGGL(kern, grid, block, lds, s, x, B, N, g->eu, g->ev, E, halve, (const WT*)ws, ws_pitch, rd_std, thresh, seed,  \
-                           env_offset, (int)draw, obj, (const uint64_t*)scratch, x_aligned);                           \
-    } while (0)
-    // (one counter width: the round is bound by its noise generation, the few carry steps a narrower counter saves per 1024
-    // edges do not show, and every instantiation is ~40 KB)
-#define DISPATCH_PR(WT)                                                                            \
-    do {                                                                                           \
-        if (sd_lds) LAUNCH_PR(WT, 24, true, false); else LAUNCH_PR(WT, 24, false, false);          \
-    } while (0)
-    if (S > 1) LAUNCH_PR(int8_t, 24, false, true);   // (WT and SD_LDS play no part once the mask is given)
-    else if (ws_bytes == 1) DISPATCH_PR(int8_t); else DISPATCH_PR(int16_t);
-#undef DISPATCH_PR
-#undef LAUNCH_PR
-    return check_launch("k_ls_propose");
+    LsShape s;   // (x_aligned: else the funnel-shift form of the row-piece stage)
+    RLS_REQUIRE(ls_shape(&s, g, B, ws_bytes, 0, 1, x, nullptr, ws, ws_pitch, scratch, scratch_bytes), RLS_EINVAL, "ws_bytes must be 1 or 2 (rls_maxcut_ls_weights writes either)");
+    return ls_run_rounds(plan_ls_propose(s), g, s, x, ws, rd_std, thresh, seed, env_offset, draw, obj, scratch, stream);
 }
 
 // num_draws proposal rounds (draws first_draw .. first_draw + num_draws - 1) in place.  A small batch with enough scratch for all
-// rounds' mask words (rls_maxcut_ls_scratch_bytes(.., num_draws)) gets them from num_draws mask launches and applies them on one
-// load of the tile; otherwise one rls_maxcut_ls_propose per round.  Same result either way.
-extern "C" int rls_maxcut_ls_rounds(const rls_graph* g, uint8_t* x, int64_t B, const void* ws, int32_t ws_bytes, int64_t ws_pitch,
-                                    const float* rd_std, const float* thresh, uint64_t seed, int64_t env_offset, int32_t first_draw,
-                                    int32_t num_draws, int64_t* obj, void* scratch, int64_t scratch_bytes, void* stream) {
+// rounds' mask words (rls_maxcut_ls_scratch_bytes(.., num_draws)) gets them from one mask launch and applies them on one load of
+// the tile; otherwise one round per propose launch.  Same result either way.
+extern "C" int rls_maxcut_ls_rounds(const rls_graph* g, uint8_t* x, int64_t B, const void* ws, int32_t ws_bytes, int64_t ws_pitch, const float* rd_std, const float* thresh,
+                                    uint64_t seed, int64_t env_offset, int32_t first_draw, int32_t num_draws, int64_t* obj, void* scratch, int64_t scratch_bytes, void* stream) {
     if (int rc = check_graph(g)) return rc;
     RLS_REQUIRE(B >= 0 && first_draw >= 0 && num_draws >= 0, RLS_EINVAL, "bad sizes");
     if (B == 0 || num_draws == 0) return RLS_OK;
     RLS_REQUIRE(x && ws && rd_std && thresh && obj, RLS_EINVAL, "NULL pointer");
-    RLS_REQUIRE(ws_bytes == 1 || ws_bytes == 2, RLS_EINVAL, "ws_bytes must be 1 or 2 (rls_maxcut_ls_weights writes either)");
-    const int64_t N = g->num_nodes, E = g->num_stored_edges;
-    if (ws_pitch == 0) ws_pitch = N;
-    const int S = ls_slices(B, ws_bytes == 1 ? ls_num_chunks<int8_t>(N) : ls_num_chunks<int16_t>(N));
-    const bool per_round = knob_on(KN_LS_PER_ROUND);   // dev knob: one propose launch per round
-    const bool half = ls_half_tile(N), narrow = ls_narrow_tile(N);
-    const bool big = ls_big_tile(N) || half || narrow;
-    RLS_REQUIRE(!(half || narrow) || ls_noise_passes_fit(N), RLS_EUNSUPPORTED, "N=%lld: rd_std does not fit LDS and N is not a multiple of 4", (long long)N);
-    const size_t one_round = (size_t)ceil_div(B, kWave) * (size_t)N * 8;
-    const bool scratch_ok = scratch && (((uintptr_t)scratch) & 15) == 0 && ls_pitch_ok(ws, ws_pitch, ws_bytes, N) && pick_planes(E) != 0;
-    RLS_REQUIRE(!big || (scratch_ok && (size_t)scratch_bytes >= one_round), RLS_EUNSUPPORTED,
-                "N=%lld: the proposal rounds need %zu bytes of scratch (rls_maxcut_ls_scratch_bytes) and ws rows on a 16-byte pitch",
-                (long long)N, one_round);
-    const bool all_at_once = !per_round && num_draws > 1 && scratch_ok && (size_t)scratch_bytes >= one_round * (size_t)num_draws &&
-                             (big || ls_propose_lds(N, false) <= (size_t)kLdsBytes);
-    if (!all_at_once && !big) {
-        for (int32_t r = 0; r < num_draws; ++r)
-            if (int rc = rls_maxcut_ls_propose(g, x, B, ws, ws_bytes, ws_pitch, rd_std, thresh, seed, env_offset, first_draw + r, obj, scratch,
-                                               scratch_bytes, stream))
-                return rc;
-        return RLS_OK;
-    }
-    const dim3 grid((unsigned)ceil_div(B, kWave)), gm(grid.x, (unsigned)S);
-    hipStream_t s = as_stream(stream);
-    const bool sd_lds = ls_noise_sd_lds(N);
-    const size_t ldm = ls_mask_lds(N, sd_lds);
-    const int halve = g->if_bidirectional ? 1 : 0, x_aligned = tile_rows_aligned(x, N, 1) ? 1 : 0;
-    const int per_launch = all_at_once ? num_draws : 1;       // rounds whose mask words are in the scratch at once
-    for (int32_t r0 = 0; r0 < num_draws; r0 += per_launch) {
-        {   // the mask words of the per_launch rounds: one launch, blockIdx.z = round
-            const dim3 block(kLsRoundWaves * kWave), gz(gm.x, gm.y, (unsigned)per_launch);
-            const int64_t round_words = (int64_t)grid.x * N;
-            if (ws_bytes == 1) {
-                auto kern = sd_lds ? k_ls_mask<int8_t, true> : k_ls_mask<int8_t, false>;
-                if (ldm > 64 * 1024) ensure_dyn_lds((const void*)kern, ldm);
-                hipLaunchKernelGGL(kern, gz, block, ldm, s, (const int8_t*)ws, ws_pitch, B, N, rd_std, thresh, seed, env_offset,
-                                   (int)(first_draw + r0), (uint64_t*)scratch, round_words);
-            } else {
-                auto kern = sd_lds ? k_ls_mask<int16_t, true> : k_ls_mask<int16_t, false>;
-                if (ldm > 64 * 1024) ensure_dyn_lds((const void*)kern, ldm);
-                hipLaunchKernelGGL(kern, gz, block, ldm, s, (const int16_t*)ws, ws_pitch, B, N, rd_std, thresh, seed, env_offset,
-                                   (int)(first_draw + r0), (uint64_t*)scratch, round_words);
-            }
-        }
-        if (int rc = check_launch("k_ls_mask")) return rc;
-        if (narrow) {   // past the half tile: each round's mask words are K6's bit-packed mask (narrow tiles there: rls_maxcut.hip)
-            for (int32_t r = 0; r < per_launch; ++r)
-                if (int rc = rls_maxcut_propose_accept(g, x, B, (const uint64_t*)scratch + (size_t)r * grid.x * (size_t)N, 1, obj, stream)) return rc;
-            continue;
-        }
-        // half tiles (twice the workgroups, the same mask words): past the 64-env tile, and for batches that leave half the CUs
-        // without a 64-env tile (whole local_search_inplace calls, 4096 envs: G22-sized 0.324 -> 0.305 ms, BA n = 10^4 0.893 -> 0.816,
-        // G70-sized 0.689 -> 0.642; at 16 384 envs no gain).  Dev knob RLS_LS_APPLY32 = 0 | 1 forces the choice.
-        const int knob32 = (int)knob(KN_LS_APPLY32, -1);
-        const bool fast32 = x_aligned && (N & 7) == 0 && ls_apply32_lds(N, kLsRoundWaves, true) <= (size_t)kLdsBytes;
-        const bool few32 = knob32 >= 0 ? knob32 != 0 : 2 * (int64_t)grid.x <= (int64_t)num_cus();
-        if (half || (few32 && fast32)) {
-            const int st32 = (x_aligned && (N & 7) == 0 && ls_apply32_lds(N, kLsRoundWaves, true) <= (size_t)kLdsBytes) ? 1 : 0;
-            const size_t lds = ls_apply32_lds(N, kLsRoundWaves, st32 != 0);
-            auto kern = k_ls_apply_rounds32<24, kLsRoundWaves>;
-            if (lds > 64 * 1024) ensure_dyn_lds((const void*)kern, lds);
-            hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(B, (int64_t)kHalf)), dim3(kLsRoundWaves * kWave), lds, s, x, B, N, g->eu, g->ev, E,
-                               halve, (const uint64_t*)scratch, (int64_t)grid.x, per_launch, obj, x_aligned, st32);
-        } else if (big) {   // the bare tile: 4 waves, lane-per-env loads and stores
-            const size_t lds = ls_apply_lds(N, 4, false);
-            auto kern = k_ls_apply_rounds<24, 4>;
-            if (lds > 64 * 1024) ensure_dyn_lds((const void*)kern, lds);
-            hipLaunchKernelGGL(kern, grid, dim3(4 * kWave), lds, s, x, B, N, g->eu, g->ev, E, halve, (const uint64_t*)scratch, per_launch, obj,
-                               x_aligned, 0);
-        } else {
-            const size_t lds = ls_apply_lds(N, kLsRoundWaves, true);
-            auto kern = k_ls_apply_rounds<24, kLsRoundWaves>;
-            if (lds > 64 * 1024) ensure_dyn_lds((const void*)kern, lds);
-            hipLaunchKernelGGL(kern, grid, dim3(kLsRoundWaves * kWave), lds, s, x, B, N, g->eu, g->ev, E, halve, (const uint64_t*)scratch,
-                               per_launch, obj, x_aligned, 1);
-        }
-        if (int rc = check_launch("k_ls_apply_rounds")) return rc;
-    }
-    return RLS_OK;
+    LsShape s;
+    RLS_REQUIRE(ls_shape(&s, g, B, ws_bytes, 0, num_draws, x, nullptr, ws, ws_pitch, scratch, scratch_bytes), RLS_EINVAL, "ws_bytes must be 1 or 2 (rls_maxcut_ls_weights writes either)");
+    return ls_run_rounds(plan_ls_rounds(s), g, s, x, ws, rd_std, thresh, seed, env_offset, first_draw, obj, scratch, stream);
 }
 
 extern "C" int rls_maxcut_ls_normals(float* out, int64_t B, int64_t N, uint64_t seed, int64_t env_offset, int32_t draw, void* stream) {

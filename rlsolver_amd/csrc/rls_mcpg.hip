@@ -1406,6 +1406,13 @@ __global__ __launch_bounds__(kStopWaves * kWave) void k_metro_stop(const int64_t
 
 using namespace rls;
 
+// a chain spin layout (spin_bytes 1 | 4, or 0 = bit-packed where PACKED allows it) as a value of its element type
+template <bool PACKED, typename F>
+static int with_spins(int spin_bytes, F&& f) {
+    if constexpr (PACKED) { if (spin_bytes == 0) return f(Packed64{}); }
+    return spin_bytes == 1 ? f(uint8_t{}) : f(float{});
+}
+
 extern "C" {
 
 int rls_mcpg_metro_rounds(void* samples, const void* samples_in, int64_t C_in, int spin_bytes, int64_t N, int64_t C,
@@ -1553,35 +1560,24 @@ int rls_mcpg_local_search_levels(const rls_graph* g, const void* xs_in, int spin
     const dim3 grid = cgrid;
     hipStream_t s = as_stream(stream);
     const int force_w = (int)knob(KN_K7_WAVES, 0);   // dev knob
-#define LAUNCH_LVL(TI, TO, PP, WW)                                                                              \
-    do {                                                                                                        \
-        auto kern = k_mcpg_local_search_levels<TI, TO, PP, WW>;                                                 \
-        if (lds > 64 * 1024)                                                                                    \
-            ensure_dyn_lds((const void*)kern, lds); \
-        hipLaunchKernelGGL(kern, grid, dim3(WW * kWave), lds, s, (const typename ChainStore<TI>::type*)xs_in,   \
-                           (typename ChainStore<TO>::type*)xs_out, N, C, tiles_in, lv_ptr, lv_data, num_groups,  \
-                           num_ls, coins, seed, g->eu, g->ev, E, expected, ids);                                 \
-    } while (0)
-#define DISPATCH_LVL(TI, TO, WW)                      \
-    switch (P) {                                      \
-        case 12: LAUNCH_LVL(TI, TO, 12, WW); break;   \
-        case 16: LAUNCH_LVL(TI, TO, 16, WW); break;   \
-        case 20: LAUNCH_LVL(TI, TO, 20, WW); break;   \
-        default: LAUNCH_LVL(TI, TO, 24, WW); break;   \
-    }
-    if (spin_bytes == 0 && out_spin_bytes == 0) {
-        const int ww = force_w ? force_w : kLvWavesPacked;
-        if (ww == 4) { DISPATCH_LVL(Packed64, Packed64, 4) }
-        else if (ww == 16) { DISPATCH_LVL(Packed64, Packed64, 16) }
-        else { DISPATCH_LVL(Packed64, Packed64, kLvWavesPacked) }
-    } else if (spin_bytes == 0) { DISPATCH_LVL(Packed64, float, kLvWaves) }
-    else if (spin_bytes == 1 && out_spin_bytes == 4) { DISPATCH_LVL(uint8_t, float, kLvWaves) }
-    else if (spin_bytes == 4 && out_spin_bytes == 4) { DISPATCH_LVL(float, float, kLvWaves) }
-    else if (spin_bytes == 1) { DISPATCH_LVL(uint8_t, Packed64, kLvWaves) }
-    else { DISPATCH_LVL(float, Packed64, kLvWaves) }
-#undef DISPATCH_LVL
-#undef LAUNCH_LVL
-    return check_launch("k_mcpg_local_search_levels");
+    auto run = [&](auto ti, auto to, auto W) {      // (ti, to: a value of the chains' element type in and out)
+        return with_value<12, 16, 20, 24>(P, [&](auto PP) {
+            using TI = decltype(ti);
+            using TO = decltype(to);
+            auto kern = k_mcpg_local_search_levels<TI, TO, PP(), W()>;
+            ensure_dyn_lds((const void*)kern, lds);
+            hipLaunchKernelGGL(kern, grid, dim3(W() * kWave), lds, s, (const typename ChainStore<TI>::type*)xs_in, (typename ChainStore<TO>::type*)xs_out, N, C,
+                               tiles_in, lv_ptr, lv_data, num_groups, num_ls, coins, seed, g->eu, g->ev, E, expected, ids);
+            return check_launch("k_mcpg_local_search_levels");
+        });
+    };
+    // packed to packed: 4, 16 or kLvWavesPacked waves; every other in / out pair: kLvWaves only
+    if (spin_bytes == 0 && out_spin_bytes == 0)
+        return with_value<4, 16, kLvWavesPacked>(force_w ? force_w : kLvWavesPacked, [&](auto W) { return run(Packed64{}, Packed64{}, W); });
+    return with_spins<true>(spin_bytes, [&](auto ti) {
+        constexpr std::integral_constant<int, kLvWaves> W{};
+        return out_spin_bytes == 0 ? run(ti, Packed64{}, W) : run(ti, float{}, W);
+    });
 }
 
 int rls_mcpg_local_search(const rls_graph* g, const void* xs_in, int spin_bytes, float* xs_out, int64_t C,
@@ -1616,49 +1612,27 @@ int rls_mcpg_local_search(const rls_graph* g, const void* xs_in, int spin_bytes,
                     "visit_len %lld is not a batched visit stream of this graph", (long long)visit_len);
         const dim3 block(kK7Waves * kWave);
         const int gn = (int)gauge_node;
-#define LAUNCH_LSS(TI, PP, WGT)                                                                                      \
-    do {                                                                                                             \
-        auto kern = k_mcpg_local_search_stream<TI, PP, WGT>;                                                         \
-        if (lds_fast > 64 * 1024)                                                                                    \
-            ensure_dyn_lds((const void*)kern, lds_fast); \
-        hipLaunchKernelGGL(kern, grid, block, lds_fast, s, (const TI*)xs_in, xs_out, N, C, visit_stream, visit_len,   \
-                           num_ls, uniforms, seed, g->eu, g->ev, edge_weights, E, gn, expected, ids);                 \
-    } while (0)
-#define DISPATCH_PS(TI)                              \
-    if (weighted) { LAUNCH_LSS(TI, 12, true); }      \
-    else switch (P) {                                \
-        case 12: LAUNCH_LSS(TI, 12, false); break;   \
-        case 16: LAUNCH_LSS(TI, 16, false); break;   \
-        case 20: LAUNCH_LSS(TI, 20, false); break;   \
-        default: LAUNCH_LSS(TI, 24, false); break;   \
-    }
-        if (spin_bytes == 1) { DISPATCH_PS(uint8_t) } else { DISPATCH_PS(float) }
-#undef DISPATCH_PS
-#undef LAUNCH_LSS
-        return check_launch("k_mcpg_local_search_stream");
+        auto run = [&](auto ti, auto PP, auto WGT) {
+            auto kern = k_mcpg_local_search_stream<decltype(ti), PP(), WGT()>;
+            ensure_dyn_lds((const void*)kern, lds_fast);
+            hipLaunchKernelGGL(kern, grid, block, lds_fast, s, (const decltype(ti)*)xs_in, xs_out, N, C, visit_stream, visit_len, num_ls, uniforms, seed, g->eu, g->ev,
+                               edge_weights, E, gn, expected, ids);
+            return check_launch("k_mcpg_local_search_stream");
+        };
+        return with_spins<false>(spin_bytes, [&](auto ti) {      // (the weighted stream: 12 planes only)
+            if (weighted) return run(ti, std::integral_constant<int, 12>{}, std::true_type{});
+            return with_value<12, 16, 20, 24>(P, [&](auto PP) { return run(ti, PP, std::false_type{}); });
+        });
     }
     const size_t lds = (size_t)N * 8 + (size_t)((N + 31) / 32) * 4 + 16;
     RLS_REQUIRE(lds <= (size_t)kLdsBytes, RLS_EUNSUPPORTED, "N=%lld needs %zu B of LDS (max %d)", (long long)N, lds,
                 kLdsBytes);
-#define LAUNCH_LS(TI, PP)                                                                                       \
-    do {                                                                                                        \
-        auto kern = k_mcpg_local_search<TI, PP>;                                                                \
-        if (lds > 64 * 1024)                                                                                    \
-            ensure_dyn_lds((const void*)kern, lds); \
-        hipLaunchKernelGGL(kern, grid, block, lds, s, (const TI*)xs_in, xs_out, N, C, g->rowptr, g->col, order, \
-                           num_ls, uniforms, seed, g->eu, g->ev, E, expected, ids);                             \
-    } while (0)
-#define DISPATCH_P(TI)                       \
-    switch (P) {                             \
-        case 12: LAUNCH_LS(TI, 12); break;   \
-        case 16: LAUNCH_LS(TI, 16); break;   \
-        case 20: LAUNCH_LS(TI, 20); break;   \
-        default: LAUNCH_LS(TI, 24); break;   \
-    }
-    if (spin_bytes == 1) { DISPATCH_P(uint8_t) } else { DISPATCH_P(float) }
-#undef DISPATCH_P
-#undef LAUNCH_LS
-    return check_launch("k_mcpg_local_search");
+    return with_spins<false>(spin_bytes, [&](auto ti) { return with_value<12, 16, 20, 24>(P, [&](auto PP) {
+        auto kern = k_mcpg_local_search<decltype(ti), PP()>;
+        ensure_dyn_lds((const void*)kern, lds);
+        hipLaunchKernelGGL(kern, grid, block, lds, s, (const decltype(ti)*)xs_in, xs_out, N, C, g->rowptr, g->col, order, num_ls, uniforms, seed, g->eu, g->ev, E,
+                           expected, ids);
+        return check_launch("k_mcpg_local_search"); }); });
 }
 
 int rls_mcpg_pick_best(const float* expected, const void* xs, int spin_bytes, int64_t N, int64_t total_mcmc_num,

@@ -4,17 +4,19 @@
 // EXACTLY-sized heap buffers, built with -fsanitize=address,undefined by tests/test_sanitize.py.  Every builder runs
 // its sizing call first and then fills buffers of exactly that size, so a one-past-the-end write is an ASAN report;
 // structural invariants (every node scheduled once, levels respect the dependency order, ELL rows complete) are checked
-// on top.  The launch planners (csrc/rls_maxcut_plan.h, rls_tsp_plan.h, rls_isco_plan.h, rls_subset_plan.h: host-only C++) run over random shapes beside them.  Exit code 0 = clean.  CPU only: sanitizers do not run on the GPU box.
+// on top.  The launch planners (csrc/rls_maxcut_plan.h, rls_ls_plan.h, rls_tsp_plan.h, rls_isco_plan.h, rls_subset_plan.h: host-only C++) run over random shapes beside them.  Exit code 0 = clean.  CPU only: sanitizers do not run on the GPU box.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <random>
 #include <set>
+#include <string>
 #include <vector>
 
 #include "rlsolver_hip.h"
 #include "rls_maxcut_plan.h"      // the MaxCut launch planner: host-only C++, so it runs under the sanitizers too
+#include "rls_ls_plan.h"          // ... and the local search's
 #include "rls_tsp_plan.h"         // ... and the TSP one
 #include "rls_isco_plan.h"        // ... and the ISCO steps'
 #include "rls_subset_plan.h"      // ... and sub_set_sampling's
@@ -279,6 +281,56 @@ static void run_planners(std::mt19937_64& rng) {
               "TSP form N %lld K %d err %d lds %zu block %d waves %d", (long long)tn, tk, p.err, p.lds, p.block, p.waves);
 }
 
+// the local-search planner over random shapes (N up to past the narrow tile, any layout flags, scratch around what the query asks for,
+// random policy knobs): a plan is a refusal with a text or launches that fit LDS; what the host queries answer -- supported, scratch
+// bytes, slices -- is what the plans do with it; rls_maxcut_ls_propose's plan is rls_maxcut_ls_rounds' with one draw
+static void run_ls_plans(std::mt19937_64& rng) {
+    using namespace rls;
+    static const char* kKnobs[] = {"RLS_LS_WAVES", "RLS_LS_SLICES", "RLS_LS_PER_ROUND", "RLS_LS_APPLY32", "RLS_LS_SD_GLOBAL", "RLS_NARROW_TILE", "RLS_SWEEP_NO_LEVELS"};
+    const uint64_t f = rng();
+    if (f & 1) rls_tuning_set(kKnobs[rng() % 7], (int64_t)(rng() % 9));
+    LsShape s{};
+    s.N = f & 2 ? 1 + (int64_t)(rng() % 170000) : 1 + (int64_t)(rng() % 26000); s.B = 1 + (int64_t)(rng() % (1 << 17)); s.E = (int64_t)(rng() % (1 << 25));
+    s.G = (int64_t)(rng() % (s.N / 32 + 2)); s.ws_bytes = f & 4 ? 1 : 2; s.num_spin = (int)(rng() % 18); s.num_draws = 1 + (int)(rng() % 9);
+    s.ws_pitch = s.N + (int64_t)(rng() % 17); s.max_degree = (int)(rng() % 600); s.cus = 1 + (int)(rng() % 512);
+    s.weighted = (f & 24) == 24; s.has_levels = f & 32; s.has_batches = f & 64; s.x_aligned = (f & 128) && (s.N & 3) == 0; s.noise16 = f & 256;
+    s.pitch_ok = ((s.ws_pitch * s.ws_bytes) & 15) == 0; s.scratch_ok = (f & 1536) != 0;
+    const size_t ask = ls_scratch_bytes(s);
+    s.scratch_bytes = f & 2048 ? ask : (f & 4096 ? (ask ? ask - 1 : 0) : (size_t)(rng() % (2 * ask + 2)));
+    const LsTile t = ls_tile(s);
+    const LsPlan plans[] = {plan_ls_fused(s), plan_ls_threshold(s), plan_ls_propose(s), plan_ls_rounds(s)};
+    for (const LsPlan& p : plans) {
+        CHECK(p.err == RLS_OK ? p.n >= 1 && p.n <= 2 && p.repeat >= 1 && p.repeat * p.per_launch == (&p == &plans[3] ? s.num_draws : 1)
+                              : p.err == RLS_EUNSUPPORTED && p.msg[0] != 0 && p.n == 0, "ls plan N %lld: err %d n %d repeat %d", (long long)s.N, p.err, p.n, p.repeat);
+        for (int i = 0; i < p.n; ++i)
+            CHECK(p.l[i].lds >= 0 && p.l[i].lds <= kLdsBytes && p.l[i].grid[0] >= 1 && p.l[i].grid[1] >= 1 && p.l[i].grid[1] <= 8 && p.l[i].grid[2] >= 1 &&
+                      (p.l[i].kernel == LSK_K6 || p.l[i].block >= 64), "ls launch N %lld kernel %d lds %lld", (long long)s.N, p.l[i].kernel, (long long)p.l[i].lds);
+    }
+    // the views: the answer of each host query is what the plans do on well-laid-out arguments with the scratch asked for
+    LsShape v = s;
+    v.pitch_ok = v.noise16 = v.scratch_ok = true; v.x_aligned = (s.N & 3) == 0; v.scratch_bytes = ask;
+    CHECK(ls_fused_supported(s) == (plan_ls_fused(v).err == RLS_OK), "fused supported N %lld", (long long)s.N);
+    const LsPlan th = plan_ls_threshold(v), all = plan_ls_rounds(v);
+    CHECK(th.err != RLS_OK || ((int)th.l[0].grid[1] == t.slices && th.n == (t.slices > 1 ? 2 : 1)), "slices N %lld: %d", (long long)s.N, t.slices);
+    if (all.err == RLS_OK && all.l[0].kernel == LSK_MASK && all.l[0].round_words != 0)
+        CHECK((int)all.l[0].grid[1] == t.slices && ask >= ls_round_bytes(s) * (size_t)all.per_launch, "mask words N %lld", (long long)s.N);
+    if (all.err == RLS_OK && s.num_draws > 1 && !knob_on(KN_LS_PER_ROUND) && ls_round_bytes(s) * (size_t)s.num_draws <= kLsMaxMaskBytes)
+        CHECK(all.per_launch == s.num_draws && all.repeat == 1, "all rounds at once N %lld draws %d", (long long)s.N, s.num_draws);
+    LsShape one = v;
+    one.num_draws = 1; one.scratch_bytes = ls_scratch_bytes(one);
+    const LsPlan r1 = plan_ls_rounds(one), pr = plan_ls_propose(one);
+    CHECK(ls_rounds_supported(s) == (ls_spin_ok(s) && r1.err == RLS_OK), "rounds supported N %lld", (long long)s.N);
+    CHECK(pr.err == r1.err && pr.n == r1.n && pr.repeat == r1.repeat && std::string(pr.msg) == r1.msg, "propose is rounds with one draw, N %lld", (long long)s.N);
+    for (int i = 0; i < r1.n; ++i)
+        CHECK(pr.l[i].kernel == r1.l[i].kernel && pr.l[i].lds == r1.l[i].lds && pr.l[i].grid[0] == r1.l[i].grid[0] && pr.l[i].grid[1] == r1.l[i].grid[1] &&
+                  pr.l[i].sd_lds == r1.l[i].sd_lds && pr.l[i].premask == r1.l[i].premask && pr.l[i].stage == r1.l[i].stage, "propose launch %d, N %lld", i, (long long)s.N);
+    if (r1.err == RLS_OK && ls_masked(t.cls)) {      // the rounds run through the mask words: not with a byte less than the query says
+        --one.scratch_bytes;
+        CHECK(plan_ls_rounds(one).err == RLS_EUNSUPPORTED, "N %lld ran short of scratch", (long long)s.N);
+    }
+    rls_tuning_unset(nullptr);
+}
+
 // the ISCO steps' planner (graph and dense) over random (N, B) up to past every LDS limit, under every combination of its four dev
 // knobs: a plan fits LDS, its lists are powers of two of at least 64 entries (or hold every node of a smaller graph, or are the
 // forced capacity), 1..8 samples share a workgroup, and only rows of >= 256 nodes in LDS get a workgroup per sample by choice
@@ -412,6 +464,7 @@ int main(int argc, char** argv) {
         run_builders(g, rng);
         run_oracle(g, rng);
         for (int k = 0; k < 50; ++k) run_planners(rng);
+        for (int k = 0; k < 50; ++k) run_ls_plans(rng);
         run_isco_plans(rng);
         run_subset_plans(rng);
         run_maxsat(rng, it);
