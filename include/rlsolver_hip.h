@@ -1020,6 +1020,33 @@ int rls_tsp_2opt_delta(const float* dist, int64_t N, const int64_t* perm, int64_
 int rls_tsp_2opt_best(const double* dist, int64_t N, const int64_t* perm, int64_t B, const double* cur_length, int32_t slices,
                       int64_t* best_i, int64_t* best_j, double* best_value, void* stream);
 
+/* One pass of local_search_3_opt  methods_problem_specific/TSP/opt_3.py:42-105 (segments_3_opt :27-37, distance_calc :17-22).
+ * The reference's move reverses blocks in place and moves none: for every triple (i, j, k), 0 <= i < j < N, j < k < N + (i > 0),
+ * in that order, the open tour perm[b] is cut into H = p[0..i], S1 = p[i+1..j], S2 = p[j+1..min(k, N-1)], C = the rest (S2 and C
+ * may be empty), and seven trials are evaluated against that same tour, numbered in the reference's order
+ *     0 aBC   1 AbC   2 ABc   3 Abc   4 abC   5 aBc   6 abc        (a lower-case letter: S1 / S2 / C reversed).
+ * The result is the first strict minimum in (i, j, k, trial) order; trials that reproduce the seed tour are evaluated too.
+ * dist float64 [N, N], N >= 3; perm int64 [B, N] open 0-based tours (permutations of 0..N-1: not checked on the device).
+ *   cur_length != NULL (float64 [B], the length the reference holds for the seed): a candidate's value is the length of its
+ *     closed tour summed as distance_calc does (float64, edge after edge from position 0, the closing edge last) -- the
+ *     reference's own comparison values, for any matrix.  best_value[b] = the winner's length (< cur_length[b]), or
+ *     cur_length[b] with (best_i, best_j, best_k, best_trial)[b] = -1 when no candidate is strictly shorter.
+ *   cur_length == NULL (SYMMETRIC dist): only the junctions between consecutive non-empty blocks change, in cyclic order H|S1,
+ *     S1|S2, S2|C, C|p[0] (an empty block is skipped).  With x_q / y_q the new / old edge of junction q = 1..m, m <= 4:
+ *     value = (((x_1 + x_2) + x_3) + x_4) - (((y_1 + y_2) + y_3) + y_4) in float64, each sum left to right, compared with 0.
+ *     best_value[b] = the most negative value, or 0 with -1 indices.
+ * slices in [1, 65535] workgroups share one tour's candidates: the five outputs must then hold slices * B entries each; the
+ * results are the first B of each (the rest is scratch: rows of [slices, B] partial results).
+ * RLS_EUNSUPPORTED where the tour no longer fits LDS (rls_tsp_3opt_launch_form).  Additive (the ABI stays v12). */
+int rls_tsp_3opt_best(const double* dist, int64_t N, const int64_t* perm, int64_t B, const double* cur_length, int32_t slices,
+                      int64_t* best_i, int64_t* best_j, int64_t* best_k, int64_t* best_trial, double* best_value, void* stream);
+
+/* [host] The form rls_tsp_3opt_best takes at N (exact = 1: cur_length given): the launcher's own arithmetic (csrc/rls_tsp3_plan.h),
+ * nothing is launched.  Fills lds_d (the float64 matrix is staged in LDS), block, waves, lds_bytes = lds_d * 8 N^2 + exact * 8 (N + 1)
+ * + 16 waves + 4 N, kernel = RLS_TSP_KERNEL_ONLY, tab8 = 0; supported = 0 (other fields 0) where the entry point returns
+ * RLS_EUNSUPPORTED.  RLS_EINVAL for N < 3 or out == NULL. */
+int rls_tsp_3opt_launch_form(int64_t N, int32_t exact, rls_tsp_form* out);
+
 /* ------------------------------------------------------------------- ISCO sampler steps */
 
 /* ISCO_maxcut.step(x, path_length, temperature)  envs/env_ISCO.py:26-49 in ONE kernel (one wave per env):

@@ -140,6 +140,8 @@ SIGNATURES = {
     "rls_tsp_apply_swap": [_P, _I64, _I64, _P, _P, _P],
     "rls_tsp_2opt_delta": [_P, _I64, _P, _I64, _P, _P, _P, _P],
     "rls_tsp_2opt_best": [_P, _I64, _P, _I64, _P, C.c_int32, _P, _P, _P, _P],
+    "rls_tsp_3opt_best": [_P, _I64, _P, _I64, _P, C.c_int32, _P, _P, _P, _P, _P, _P],
+    "rls_tsp_3opt_launch_form": [_I64, C.c_int32, _P],
     "rls_rand_perms": [_P, _I64, _I64, _U64, _I64, _P],
     "rls_isco_maxcut_step": [_G, _P, _P, _I64, _P, _F32, _P, _P, _U64, _I64, _P, _P, _P, _P, _P, _I64, _P],
     "rls_isco_mis_step": [_G, _P, _P, _I64, _P, _F32, _F32, _P, _P, _U64, _I64, _P, _P, _P, _P, _P, _I64, _P],
@@ -231,6 +233,13 @@ def tsp_launch_form(what: int, N: int, K: int = 0, has_tables8: bool = False) ->
     """The form a TSP entry point takes at these sizes (rls_tsp_launch_form: the launchers' own arithmetic, nothing is launched)."""
     f = RlsTspForm()
     call("rls_tsp_launch_form", int(what), int(N), int(K), int(bool(has_tables8)), C.byref(f))
+    return f
+
+
+def tsp_3opt_launch_form(N: int, exact: bool) -> RlsTspForm:
+    """The form rls_tsp_3opt_best takes at N (rls_tsp_3opt_launch_form: the launcher's own arithmetic, nothing is launched)."""
+    f = RlsTspForm()
+    call("rls_tsp_3opt_launch_form", int(N), int(bool(exact)), C.byref(f))
     return f
 
 

@@ -1147,6 +1147,33 @@ void tsp_2opt_best(const Tensor& dist, const Tensor& perm, const OptTensor& cur_
     ok(rls_tsp_2opt_best((const double*)p(dist), perm.size(1), (const int64_t*)p(perm), perm.size(0), (const double*)p(cur_length), (int32_t)slices,
                          (int64_t*)p(best_i), (int64_t*)p(best_j), (double*)p(best_value), cur_stream(perm)), "rls_tsp_2opt_best");
 }
+// the five outputs hold slices * B entries each: rows of [slices, B] partial results, the results in row 0 (slices is read off best_i)
+void tsp_3opt_best(const Tensor& dist, const Tensor& perm, const OptTensor& cur_length, Tensor best_i, Tensor best_j, Tensor best_k,
+                   Tensor best_trial, Tensor best_value) {
+    perm_and_dist(dist, perm, F64);
+    TORCH_CHECK(perm.size(1) >= 3, "perm must hold tours of N >= 3 cities");
+    optdev(cur_length, "cur_length", F64);
+    dev(best_i, "best_i", I64);
+    dev(best_j, "best_j", I64);
+    dev(best_k, "best_k", I64);
+    dev(best_trial, "best_trial", I64);
+    dev(best_value, "best_value", F64);
+    const int64_t B = perm.size(0);
+    const int64_t slices = B > 0 ? best_i.numel() / B : 1;
+    TORCH_CHECK(slices >= 1 && slices <= 65535, "slices = best_i.numel() / B must be in [1, 65535]");
+    count(best_i, "best_i", slices * B);
+    count(best_j, "best_j", slices * B);
+    count(best_k, "best_k", slices * B);
+    count(best_trial, "best_trial", slices * B);
+    count(best_value, "best_value", slices * B);
+    if (cur_length.has_value()) count(*cur_length, "cur_length", B);
+    on_device_of(perm, "dist", dist, "cur_length", cur_length, "best_i", best_i, "best_j", best_j, "best_k", best_k, "best_trial", best_trial,
+                 "best_value", best_value);
+    RLS_GUARD(perm);
+    ok(rls_tsp_3opt_best((const double*)p(dist), perm.size(1), (const int64_t*)p(perm), B, (const double*)p(cur_length), (int32_t)slices,
+                         (int64_t*)p(best_i), (int64_t*)p(best_j), (int64_t*)p(best_k), (int64_t*)p(best_trial), (double*)p(best_value),
+                         cur_stream(perm)), "rls_tsp_3opt_best");
+}
 void tsp_2opt_delta(const Tensor& dist, const Tensor& perm, const Tensor& i, const Tensor& j, Tensor delta) {
     perm_and_dist(dist, perm, F32);
     dev(i, "i", I64);
@@ -1374,6 +1401,8 @@ TORCH_LIBRARY(rlsolver_hip, m) {
     m.def("tsp_apply_swap(Tensor(a!) perm, Tensor pos, Tensor indices) -> ()");
     m.def("tsp_2opt_delta(Tensor dist, Tensor perm, Tensor i, Tensor j, Tensor(a!) delta) -> ()");
     m.def("tsp_2opt_best(Tensor dist, Tensor perm, Tensor? cur_length, Tensor(a!) best_i, Tensor(b!) best_j, Tensor(c!) best_value) -> ()");
+    m.def("tsp_3opt_best(Tensor dist, Tensor perm, Tensor? cur_length, Tensor(a!) best_i, Tensor(b!) best_j, Tensor(c!) best_k, "
+          "Tensor(d!) best_trial, Tensor(e!) best_value) -> ()");
     m.def("isco_maxcut_step(int graph, Tensor x, Tensor(a!) y_out, Tensor path_length, float temperature, Tensor? u_gumbel, Tensor? u_accept, "
           "int seed, int env_offset, Tensor(b!)? energy_out, Tensor(c!)? acc_out, Tensor(d!)? terms_out, Tensor(e!)? mask_out, Tensor(f!)? scratch=None) -> ()");
     m.def("maxsat_local_search(Tensor xs_in, int C_in, Tensor(a!) xs_out, int C, Tensor lv_ptr, Tensor lv_data, int num_ls, Tensor? coins, "
@@ -1450,6 +1479,7 @@ TORCH_LIBRARY_IMPL(rlsolver_hip, CUDA, m) {   // "CUDA" is the HIP dispatch key 
     m.impl("tsp_apply_swap", &tsp_apply_swap);
     m.impl("tsp_2opt_delta", &tsp_2opt_delta);
     m.impl("tsp_2opt_best", &tsp_2opt_best);
+    m.impl("tsp_3opt_best", &tsp_3opt_best);
     m.impl("isco_maxcut_step", &isco_maxcut_step);
     m.impl("isco_mis_step", &isco_mis_step);
     m.impl("maxsat_local_search", &maxsat_local_search);

@@ -6,6 +6,7 @@ from typing import Optional
 
 import torch
 
+from . import _abi
 from .ops import DeviceGraph, _check, _ptr, _s64, _stream, _t  # noqa: F401  (_ptr / _stream: raw C-ABI calls in tests)
 
 TEN = torch.Tensor
@@ -490,3 +491,41 @@ def tsp_2opt_best(dist64: TEN, perm: TEN, cur_length: Optional[TEN] = None, slic
     bv = torch.empty(slices * B, dtype=torch.float64, device=dev)
     _t.tsp_2opt_best(dist64, perm, cur_length, bi, bj, bv)
     return bi[:B], bj[:B], bv[:B]
+
+
+def tsp_3opt_default_slices(N: int, B: int, exact: bool) -> int:
+    """Workgroups per tour when the caller names none: ~512 in all, and a wave gets at least one item of the kernel's work list
+    -- whole-length ranking: a chunk of 64 triples (about C(N, 3) / 64 + N of them: every i ends on a ragged one), O(N) per
+    candidate; deltas: an (i, j) pair, N (N - 1) / 2 of them, and at least 8 per wave."""
+    items = (N * (N - 1) * (N - 2) // 6 + (N - 1) * (N - 2) // 2) // 64 + N if exact else N * (N - 1) // 2
+    per_wg = max(1, _abi.tsp_3opt_launch_form(N, exact).waves) * (1 if exact else 8)
+    return max(1, min(512 // max(B, 1), (items + per_wg - 1) // per_wg))
+
+
+def tsp_3opt_best(dist64: TEN, perm: TEN, cur_length: Optional[TEN] = None, slices: Optional[int] = None):
+    """One best-improvement pass of the reference's 3-opt per tour (rls_tsp_3opt_best, opt_3.py:42-105): over all triples
+    (i, j, k) of segments_3_opt(N) and the seven in-place reversals of S1 / S2 / C (trial 0..6 = aBC AbC ABc Abc abC aBc abc)
+    -> (best_i, best_j, best_k, best_trial int64 [B], best_value f64 [B]), the first strict minimum in (i, j, k, trial) order.
+    ``cur_length`` f64 [B]: candidates ranked by their whole length summed as the reference's distance_calc does;
+    best_value = the winner's length, or cur_length and -1 indices where none is shorter.  Without it: ranked by the
+    junction delta (symmetric dist); best_value = the most negative delta, or 0.
+    ``slices`` workgroups share one tour's (i, j) pairs (default: a lone tour spreads over the chip)."""
+    dev = perm.device
+    _check(dist64, "dist", (torch.float64,), dev)
+    _check(perm, "perm", (torch.int64,), dev)
+    if perm.dim() != 2:
+        raise ValueError("perm must be [B, N]")
+    B, N = perm.shape
+    if N < 3:
+        raise ValueError(f"tsp_3opt_best needs N >= 3 cities, got {N}")
+    if dist64.shape != (N, N):
+        raise ValueError(f"dist must be [{N}, {N}]")
+    if cur_length is not None:
+        _check(cur_length, "cur_length", (torch.float64,), dev, (B,))
+    slices = tsp_3opt_default_slices(N, B, cur_length is not None) if slices is None else int(slices)
+    if not 1 <= slices <= 65535:
+        raise ValueError(f"slices = {slices} outside [1, 65535]")
+    out = [torch.empty(slices * B, dtype=torch.int64, device=dev) for _ in range(4)]
+    bv = torch.empty(slices * B, dtype=torch.float64, device=dev)
+    _t.tsp_3opt_best(dist64, perm, cur_length, out[0], out[1], out[2], out[3], bv)
+    return out[0][:B], out[1][:B], out[2][:B], out[3][:B], bv[:B]
