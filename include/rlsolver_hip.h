@@ -1047,6 +1047,44 @@ int rls_tsp_3opt_best(const double* dist, int64_t N, const int64_t* perm, int64_
  * RLS_EUNSUPPORTED.  RLS_EINVAL for N < 3 or out == NULL. */
 int rls_tsp_3opt_launch_form(int64_t N, int32_t exact, rls_tsp_form* out);
 
+/* The order in which the constructors of methods_problem_specific/TSP take up cities: nn.py:62-75 (nearest_neighbour),
+ * ins_n.py:84-96 (nearest_insertion), ins_f.py:84-96 (farthest_insertion, farthest = 1).  chain[s, 0] = start[s] and chain[s, k + 1]
+ * = the city c not yet in the chain with the smallest (farthest = 1: largest) dist[chain[s, k], c]; among equal values the lowest
+ * city index (numpy's first extremum -- the reference masks visited rows, columns and the diagonal with +-inf, which leaves exactly
+ * these cities).  dist float64 [N, N] with finite entries, N >= 2; start int64 [S]; chain int64 [S, N]; status int32 [S]: 0, or 2
+ * where start[s] lies outside [0, N) -- that row of chain is then left as it was and nothing is read out of bounds.
+ * One wave per start, N sequential steps.  RLS_EUNSUPPORTED for N > 163840 (a byte per city in LDS).  Additive (the ABI stays v12). */
+int rls_tsp_neighbour_chain(const double* dist, int64_t N, const int64_t* start, int64_t S, int32_t farthest, int64_t* chain,
+                            int32_t* status, void* stream);
+
+/* Grow-and-converge: the inner work of nearest_insertion / farthest_insertion / cheapest_insertion (best_insertion ins_n.py:61-68,
+ * ins_c.py:61-84) and of nearest_neighbour's local search (nn.py:80-81), one persistent workgroup per row, one launch.
+ * For row s the open tour starts as order[s, 0:m_seed]; then for m = m_seed .. m_end:
+ *     if m > m_seed, order[s, m - 1] is appended at the end of the tour;
+ *     if m >= first_m, best-improvement 2-opt passes of opt_2.py:27-57 run on the closed m-city tour until a pass finds nothing
+ *     strictly shorter than the tour's length -- a pass is rls_tsp_2opt_best with cur_length given, bit for bit: every reversal
+ *     [i..j], 0 <= i < j <= m - 1, valued by distance_calc's sequential float64 sum from the candidate's first city, the first
+ *     strict minimum in (i, j) order kept.
+ * dist float64 [N, N] (N is the matrix stride, m the tour length); order int64 [S, N]; 2 <= m_seed <= m_end <= N; first_m any
+ * (> m_end: no pass at all); max_passes >= 1.
+ *   tours int64 [S, N]: tours[s, :m_end] the tour, tours[s, m_end:] = order[s, m_end:] (a permutation stays one);
+ *   length float64 [S]: the sequential float64 sum of the closed tour from tours[s, 0], the closing edge last;
+ *   passes int64 [S]: evaluated passes, the fruitless one that ends each convergence included;
+ *   status int32 [S]: 0; 1: a convergence reached max_passes improving passes -- the row holds the state after that pass (the
+ *     cities appended so far, the rest of order behind them) and grows no further.  The loop ends by itself, lengths strictly
+ *     decrease: max_passes only guarantees that the kernel returns; 2: an entry of order[s] lies outside [0, N): tours, length and
+ *     passes of the row are left as they were.  Repeated cities in a row are not detected (they index inside dist).
+ * The matrix is staged in LDS while it fits (rls_tsp_grow_launch_form); RLS_EUNSUPPORTED where even the tour no longer does.
+ * Additive (the ABI stays v12). */
+int rls_tsp_grow_2opt(const double* dist, int64_t N, const int64_t* order, int64_t S, int64_t m_seed, int64_t m_end, int64_t first_m,
+                      int64_t max_passes, int64_t* tours, double* length, int64_t* passes, int32_t* status, void* stream);
+
+/* [host] The form rls_tsp_grow_2opt takes at N: the launcher's own arithmetic (csrc/rls_tsp_grow_plan.h), nothing is launched.
+ * Fills lds_d (the float64 matrix is staged in LDS: N <= 141), block = 1024, waves = 16, lds_bytes = lds_d * 8 N^2 + 8 (N + 1)
+ * + 16 waves + 8 N, kernel = RLS_TSP_KERNEL_ONLY, tab8 = 0; supported = 0 (other fields 0) where the entry point returns
+ * RLS_EUNSUPPORTED (N >= 10224).  RLS_EINVAL for N < 2 or out == NULL. */
+int rls_tsp_grow_launch_form(int64_t N, rls_tsp_form* out);
+
 /* ------------------------------------------------------------------- ISCO sampler steps */
 
 /* ISCO_maxcut.step(x, path_length, temperature)  envs/env_ISCO.py:26-49 in ONE kernel (one wave per env):

@@ -142,6 +142,9 @@ SIGNATURES = {
     "rls_tsp_2opt_best": [_P, _I64, _P, _I64, _P, C.c_int32, _P, _P, _P, _P],
     "rls_tsp_3opt_best": [_P, _I64, _P, _I64, _P, C.c_int32, _P, _P, _P, _P, _P, _P],
     "rls_tsp_3opt_launch_form": [_I64, C.c_int32, _P],
+    "rls_tsp_neighbour_chain": [_P, _I64, _P, _I64, C.c_int32, _P, _P, _P],
+    "rls_tsp_grow_2opt": [_P, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P],
+    "rls_tsp_grow_launch_form": [_I64, _P],
     "rls_rand_perms": [_P, _I64, _I64, _U64, _I64, _P],
     "rls_isco_maxcut_step": [_G, _P, _P, _I64, _P, _F32, _P, _P, _U64, _I64, _P, _P, _P, _P, _P, _I64, _P],
     "rls_isco_mis_step": [_G, _P, _P, _I64, _P, _F32, _F32, _P, _P, _U64, _I64, _P, _P, _P, _P, _P, _I64, _P],
@@ -240,6 +243,13 @@ def tsp_3opt_launch_form(N: int, exact: bool) -> RlsTspForm:
     """The form rls_tsp_3opt_best takes at N (rls_tsp_3opt_launch_form: the launcher's own arithmetic, nothing is launched)."""
     f = RlsTspForm()
     call("rls_tsp_3opt_launch_form", int(N), int(bool(exact)), C.byref(f))
+    return f
+
+
+def tsp_grow_launch_form(N: int) -> RlsTspForm:
+    """The form rls_tsp_grow_2opt takes at N (rls_tsp_grow_launch_form: the launcher's own arithmetic, nothing is launched)."""
+    f = RlsTspForm()
+    call("rls_tsp_grow_launch_form", int(N), C.byref(f))
     return f
 
 

@@ -23,7 +23,7 @@ OPS_PATH = os.path.join(PKG_DIR, OPS_NAME)
 OPS_SRC = os.path.join(CSRC, "torch_ops.cpp")
 ARCH = "gfx950"
 
-SOURCES = ["rls_host.cpp", "rls_abi.hip", "rls_maxcut.hip", "rls_step.hip", "rls_mcpg.hip", "rls_tsp.hip", "rls_qubo.hip", "rls_spin.hip", "rls_localsearch.hip", "rls_isco.hip", "rls_pisco.hip", "rls_track.hip", "rls_maxsat.hip", "rls_cheeger.hip", "rls_maxcut_edge.hip", "rls_subset.hip", "rls_s2vppo.hip", "rls_exhaustive.hip", "rls_tsp3.hip"]
+SOURCES = ["rls_host.cpp", "rls_abi.hip", "rls_maxcut.hip", "rls_step.hip", "rls_mcpg.hip", "rls_tsp.hip", "rls_qubo.hip", "rls_spin.hip", "rls_localsearch.hip", "rls_isco.hip", "rls_pisco.hip", "rls_track.hip", "rls_maxsat.hip", "rls_cheeger.hip", "rls_maxcut_edge.hip", "rls_subset.hip", "rls_s2vppo.hip", "rls_exhaustive.hip", "rls_tsp3.hip", "rls_tsp_grow.hip"]
 
 
 def _hipcc() -> str:

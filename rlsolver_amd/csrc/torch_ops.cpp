@@ -1174,6 +1174,50 @@ void tsp_3opt_best(const Tensor& dist, const Tensor& perm, const OptTensor& cur_
                          (int64_t*)p(best_i), (int64_t*)p(best_j), (int64_t*)p(best_k), (int64_t*)p(best_trial), (double*)p(best_value),
                          cur_stream(perm)), "rls_tsp_3opt_best");
 }
+// the order in which the constructors take up cities: chain[s] from start[s]; status[s] = 2 and the row untouched where start[s] is no city
+void tsp_neighbour_chain(const Tensor& dist, const Tensor& start, int64_t farthest, Tensor chain, Tensor status) {
+    dev(dist, "dist", F64);
+    dev(start, "start", I64);
+    dev(chain, "chain", I64);
+    dev(status, "status", at::kInt);
+    TORCH_CHECK(dist.dim() == 2 && dist.size(0) == dist.size(1) && dist.size(0) >= 2, "dist must be square [N, N] with N >= 2, got ", dist.sizes());
+    TORCH_CHECK(start.dim() == 1, "start must be [S], got ", start.sizes());
+    TORCH_CHECK(farthest == 0 || farthest == 1, "farthest must be 0 or 1");
+    const int64_t N = dist.size(0), S = start.size(0);
+    shape2(chain, "chain", S, N);
+    TORCH_CHECK(status.dim() == 1, "status must be [S], got ", status.sizes());
+    count(status, "status", S);
+    on_device_of(dist, "start", start, "chain", chain, "status", status);
+    RLS_GUARD(dist);
+    ok(rls_tsp_neighbour_chain((const double*)p(dist), N, (const int64_t*)p(start), S, (int32_t)farthest, (int64_t*)p(chain), (int32_t*)p(status),
+                               cur_stream(dist)), "rls_tsp_neighbour_chain");
+}
+// grow-and-converge: row s of order joins its tour city by city, 2-opted to convergence at every size from first_m on
+void tsp_grow_2opt(const Tensor& dist, const Tensor& order, int64_t m_seed, int64_t m_end, int64_t first_m, int64_t max_passes, Tensor tours,
+                   Tensor length, Tensor passes, Tensor status) {
+    dev(dist, "dist", F64);
+    dev(order, "order", I64);
+    dev(tours, "tours", I64);
+    dev(length, "length", F64);
+    dev(passes, "passes", I64);
+    dev(status, "status", at::kInt);
+    TORCH_CHECK(dist.dim() == 2 && dist.size(0) == dist.size(1) && dist.size(0) >= 2, "dist must be square [N, N] with N >= 2, got ", dist.sizes());
+    const int64_t N = dist.size(0);
+    TORCH_CHECK(order.dim() == 2 && order.size(1) == N, "order must be [S, ", N, "], got ", order.sizes());
+    const int64_t S = order.size(0);
+    shape2(tours, "tours", S, N);
+    TORCH_CHECK(length.dim() == 1 && passes.dim() == 1 && status.dim() == 1, "length, passes and status must be [S]");
+    count(length, "length", S);
+    count(passes, "passes", S);
+    count(status, "status", S);
+    TORCH_CHECK(2 <= m_seed && m_seed <= m_end && m_end <= N, "need 2 <= m_seed <= m_end <= N");
+    TORCH_CHECK(max_passes >= 1, "max_passes must be >= 1");
+    TORCH_CHECK(tours.data_ptr() != order.data_ptr() || S == 0, "tours must not alias order");
+    on_device_of(dist, "order", order, "tours", tours, "length", length, "passes", passes, "status", status);
+    RLS_GUARD(dist);
+    ok(rls_tsp_grow_2opt((const double*)p(dist), N, (const int64_t*)p(order), S, m_seed, m_end, first_m, max_passes, (int64_t*)p(tours),
+                         (double*)p(length), (int64_t*)p(passes), (int32_t*)p(status), cur_stream(dist)), "rls_tsp_grow_2opt");
+}
 void tsp_2opt_delta(const Tensor& dist, const Tensor& perm, const Tensor& i, const Tensor& j, Tensor delta) {
     perm_and_dist(dist, perm, F32);
     dev(i, "i", I64);
@@ -1403,6 +1447,9 @@ TORCH_LIBRARY(rlsolver_hip, m) {
     m.def("tsp_2opt_best(Tensor dist, Tensor perm, Tensor? cur_length, Tensor(a!) best_i, Tensor(b!) best_j, Tensor(c!) best_value) -> ()");
     m.def("tsp_3opt_best(Tensor dist, Tensor perm, Tensor? cur_length, Tensor(a!) best_i, Tensor(b!) best_j, Tensor(c!) best_k, "
           "Tensor(d!) best_trial, Tensor(e!) best_value) -> ()");
+    m.def("tsp_neighbour_chain(Tensor dist, Tensor start, int farthest, Tensor(a!) chain, Tensor(b!) status) -> ()");
+    m.def("tsp_grow_2opt(Tensor dist, Tensor order, int m_seed, int m_end, int first_m, int max_passes, Tensor(a!) tours, Tensor(b!) length, "
+          "Tensor(c!) passes, Tensor(d!) status) -> ()");
     m.def("isco_maxcut_step(int graph, Tensor x, Tensor(a!) y_out, Tensor path_length, float temperature, Tensor? u_gumbel, Tensor? u_accept, "
           "int seed, int env_offset, Tensor(b!)? energy_out, Tensor(c!)? acc_out, Tensor(d!)? terms_out, Tensor(e!)? mask_out, Tensor(f!)? scratch=None) -> ()");
     m.def("maxsat_local_search(Tensor xs_in, int C_in, Tensor(a!) xs_out, int C, Tensor lv_ptr, Tensor lv_data, int num_ls, Tensor? coins, "
@@ -1480,6 +1527,8 @@ TORCH_LIBRARY_IMPL(rlsolver_hip, CUDA, m) {   // "CUDA" is the HIP dispatch key 
     m.impl("tsp_2opt_delta", &tsp_2opt_delta);
     m.impl("tsp_2opt_best", &tsp_2opt_best);
     m.impl("tsp_3opt_best", &tsp_3opt_best);
+    m.impl("tsp_neighbour_chain", &tsp_neighbour_chain);
+    m.impl("tsp_grow_2opt", &tsp_grow_2opt);
     m.impl("isco_maxcut_step", &isco_maxcut_step);
     m.impl("isco_mis_step", &isco_mis_step);
     m.impl("maxsat_local_search", &maxsat_local_search);

@@ -529,3 +529,54 @@ def tsp_3opt_best(dist64: TEN, perm: TEN, cur_length: Optional[TEN] = None, slic
     bv = torch.empty(slices * B, dtype=torch.float64, device=dev)
     _t.tsp_3opt_best(dist64, perm, cur_length, out[0], out[1], out[2], out[3], bv)
     return out[0][:B], out[1][:B], out[2][:B], out[3][:B], bv[:B]
+
+
+def tsp_neighbour_chain(dist64: TEN, start: TEN, farthest: bool = False):
+    """The order in which the reference's constructors take up cities (rls_tsp_neighbour_chain; nn.py:62-75, ins_f.py:84-96):
+    chain[s, 0] = start[s], chain[s, k + 1] = the nearest (``farthest``: farthest) city to chain[s, k] not yet in the chain, the
+    lowest index among equals.  -> (chain int64 [S, N], status int32 [S]); status 2 where start[s] lies outside [0, N): that row
+    of chain is then zeros."""
+    _check(dist64, "dist", (torch.float64,))
+    dev = dist64.device
+    if dist64.dim() != 2 or dist64.shape[0] != dist64.shape[1] or dist64.shape[0] < 2:
+        raise ValueError(f"dist must be square [N, N] with N >= 2, got {tuple(dist64.shape)}")
+    _check(start, "start", (torch.int64,), dev)
+    if start.dim() != 1:
+        raise ValueError("start must be [S]")
+    S, N = start.shape[0], dist64.shape[0]
+    chain = torch.zeros((S, N), dtype=torch.int64, device=dev)
+    status = torch.empty(S, dtype=torch.int32, device=dev)
+    _t.tsp_neighbour_chain(dist64, start, int(bool(farthest)), chain, status)
+    return chain, status
+
+
+def tsp_grow_2opt(dist64: TEN, order: TEN, m_seed: int = 2, m_end: Optional[int] = None, first_m: int = 3, max_passes: Optional[int] = None,
+                  out=None):
+    """Grow-and-converge (rls_tsp_grow_2opt): row s starts as order[s, :m_seed], takes order[s, m - 1] at its end for m = m_seed + 1
+    .. m_end, and from m = first_m on is 2-opted (the exact ranking of tsp_2opt_best) until a pass brings nothing, all in one launch.
+    -> (tours int64 [S, N], length f64 [S], passes int64 [S], status int32 [S]); status 1: a convergence reached ``max_passes``
+    (default N^2, a guard and no tuning value); 2: an entry of the row outside [0, N), its outputs untouched.  ``out``: the four
+    output tensors to write into (default: new ones, tours / length / passes zeroed)."""
+    _check(dist64, "dist", (torch.float64,))
+    dev = dist64.device
+    if dist64.dim() != 2 or dist64.shape[0] != dist64.shape[1] or dist64.shape[0] < 2:
+        raise ValueError(f"dist must be square [N, N] with N >= 2, got {tuple(dist64.shape)}")
+    N = dist64.shape[0]
+    _check(order, "order", (torch.int64,), dev)
+    if order.dim() != 2 or order.shape[1] != N:
+        raise ValueError(f"order must be [S, {N}]")
+    S = order.shape[0]
+    m_end = N if m_end is None else int(m_end)
+    max_passes = N * N if max_passes is None else int(max_passes)
+    if not 2 <= int(m_seed) <= m_end <= N:
+        raise ValueError(f"need 2 <= m_seed = {m_seed} <= m_end = {m_end} <= N = {N}")
+    if max_passes < 1:
+        raise ValueError(f"max_passes = {max_passes} must be >= 1")
+    if not _abi.tsp_grow_launch_form(N).supported:
+        raise ValueError(f"N = {N} is beyond the LDS limit of rls_tsp_grow_2opt (rls_tsp_grow_launch_form)")
+    if out is None:
+        out = (torch.zeros((S, N), dtype=torch.int64, device=dev), torch.zeros(S, dtype=torch.float64, device=dev),
+               torch.zeros(S, dtype=torch.int64, device=dev), torch.empty(S, dtype=torch.int32, device=dev))
+    tours, length, passes, status = out
+    _t.tsp_grow_2opt(dist64, order, int(m_seed), m_end, int(first_m), max_passes, tours, length, passes, status)
+    return tours, length, passes, status

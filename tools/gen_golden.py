@@ -2162,7 +2162,15 @@ def gen_tsp_3opt():
     gen_golden_tsp3opt.generate(save)
 
 
-ALL = {"tsp_3opt": gen_tsp_3opt, "spin_exhaustive": gen_spin_exhaustive, "s2v_ppo": gen_s2v_ppo, "sub_set_sampling": gen_sub_set_sampling, "graph_forms": gen_graph_forms, "mimo": gen_mimo, "cheeger": gen_cheeger, "maxcut_edge": gen_maxcut_edge, "maxsat": gen_maxsat, "mcpg_weighted": gen_mcpg_weighted, "isco_steps": gen_isco_steps, "isco_mis": gen_isco_mis, "spinsystem_cpu": gen_spinsystem_cpu, "spinsystem": gen_spinsystem, "spinsystem_perenv": gen_spinsystem_perenv, "qubo": gen_qubo, "qubo_asym": gen_qubo_asym, "isco_maxcut": gen_isco_maxcut, "maxcut": gen_maxcut, "sweep": gen_sweep, "lsclass": gen_local_search_class, "ppo": gen_ppo,
+def gen_tsp_construct():
+    """nearest_neighbour, nearest_insertion, farthest_insertion and cheapest_insertion of methods_problem_specific/TSP (nn.py, ins_n.py,
+    ins_f.py, ins_c.py): tools/gen_golden_tsp_construct.py (beside this file)."""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import gen_golden_tsp_construct
+    gen_golden_tsp_construct.generate(save)
+
+
+ALL = {"tsp_construct": gen_tsp_construct, "tsp_3opt": gen_tsp_3opt, "spin_exhaustive": gen_spin_exhaustive, "s2v_ppo": gen_s2v_ppo, "sub_set_sampling": gen_sub_set_sampling, "graph_forms": gen_graph_forms, "mimo": gen_mimo, "cheeger": gen_cheeger, "maxcut_edge": gen_maxcut_edge, "maxsat": gen_maxsat, "mcpg_weighted": gen_mcpg_weighted, "isco_steps": gen_isco_steps, "isco_mis": gen_isco_mis, "spinsystem_cpu": gen_spinsystem_cpu, "spinsystem": gen_spinsystem, "spinsystem_perenv": gen_spinsystem_perenv, "qubo": gen_qubo, "qubo_asym": gen_qubo_asym, "isco_maxcut": gen_isco_maxcut, "maxcut": gen_maxcut, "sweep": gen_sweep, "lsclass": gen_local_search_class, "ppo": gen_ppo,
        "select": gen_select, "mcpg": gen_mcpg, "tsp": gen_tsp, "tsp_2opt": gen_tsp_2opt, "encoder": gen_encoder,
        "wgain": gen_weighted_gain, "mcpg_glue": gen_mcpg_glue, "evaluator": gen_evaluator, "spinsystem_options": gen_spinsystem_options,
        "api_surface": gen_api_surface, "mcpg_data": gen_mcpg_data, "pisco": gen_pisco,
