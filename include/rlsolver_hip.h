@@ -189,6 +189,12 @@ int rls_maxcut_step(const rls_graph* g, const void* x_in, void* x_out, int spin_
                     float* reward, float* cur, float* done, float done_value,
                     void* stream);
 
+/* [host] The block of runs that workgroup `block` of a one-shot grid of `nblocks` workgroups works on in rls_maxcut_step's
+ * write-through form (csrc/rls_step_plan.h, the function the kernels call): order 0 = forward (the block itself), 1 = xcd-fwd
+ * (the workgroups with equal block % 8 take one contiguous range).  A bijection on [0, nblocks) for every nblocks; nothing is
+ * launched, no device is needed -- what tests pin the map with.  Additive (ABI 12). */
+int rls_maxcut_step_block(int32_t order, int64_t block, int64_t nblocks, int64_t* vblock);
+
 /* K5  greedy single-flip sweep ("addition" loop)  envs/env_L2A.py:109-116,
  *     methods/LocalSearch.py:77-83:  for i in 0..N-1: flip i if the cut does
  *     not decrease (ties accept, update_xs_by_vs uses ge, util_read_data.py:199).

@@ -161,6 +161,7 @@ SIGNATURES = {
     "rls_winner_message": [_P, _I64, _I64, _P, _P, C.c_int32, _I64, _I64, _P, _P],
     "rls_winner_unpack": [_P, _I64, _P, _P, _P],
     "rls_maxcut_launch_plan": [_G, C.c_int32, _I64, C.c_int32, C.c_int32, _P],
+    "rls_maxcut_step_block": [C.c_int32, _I64, _I64, _P],
     "rls_maxcut_ls_launch_plan": [_G, C.c_int32, _I64, C.c_int32, _I64, C.c_int32, C.c_int32, C.c_int32, _I64, C.c_int32, _P, C.c_int32, _P],
     "rls_tsp_launch_form": [C.c_int32, _I64, C.c_int32, C.c_int32, _P],
     "rls_tuning_set": [_P, _I64],

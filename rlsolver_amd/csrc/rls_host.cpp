@@ -6,6 +6,7 @@
 #include "rls_subset_plan.h"
 #include "rls_s2vppo_plan.h"
 #include "rls_isco_plan.h"
+#include "rls_step_plan.h"
 #include <cstdarg>
 #include <cstdio>
 #include <algorithm>
@@ -187,6 +188,13 @@ int rls_tuning_get(const char* name, int64_t* value, int32_t* is_set) {
 int rls_tuning_name(int32_t index, const char** name) {
     if (!name || index < 0 || index >= rls::KN_COUNT) return rls::fail(RLS_EINVAL, "rls_tuning_name: index out of range");
     *name = rls::kKnobNames[index];
+    return RLS_OK;
+}
+
+int rls_maxcut_step_block(int32_t order, int64_t block, int64_t nblocks, int64_t* vblock) {
+    if (!vblock || (order != rls::kStepOrderFwd && order != rls::kStepOrderXcdFwd) || nblocks <= 0 || block < 0 || block >= nblocks)
+        return rls::fail(RLS_EINVAL, "rls_maxcut_step_block: order 0 | 1, 0 <= block < nblocks and an output are needed");
+    *vblock = rls::step_block(order, block, nblocks);
     return RLS_OK;
 }
 

@@ -18,6 +18,7 @@
 // reads all bytes of the gain from LDS before one wait and flips with one LDS write; a call with full runs,
 // no cur / done and no CSR row longer than a wave runs that trip as a kernel of its own, k_maxcut_step_lean.
 #include "rls_tile.h"
+#include "rls_step_plan.h"
 #include <cstdlib>
 
 namespace rls {
@@ -113,7 +114,14 @@ __global__ __launch_bounds__(256) void k_maxcut_step(const T* __restrict__ xin, 
     // still in flight while the loads of run k + 1 are issued (the LDS stage is free once its ds_reads have returned), and no
     // workgroup is dispatched or retired mid-kernel
     const int64_t wave_stride = (int64_t)gridDim.x * (blockDim.x / kWave);
-  for (int64_t wave = (int64_t)blockIdx.x * (blockDim.x / kWave) + wib; wave * EPW < B; wave += wave_stride) {
+    // the headline's form takes two flags in align_lines: bit 0 the alignment on lines, bit 1 the block order xcd-fwd of
+    // rls_step_plan.h, which the launcher asks for on a one-shot grid only (one trip of this loop); every other form: 0 | 1
+    constexpr bool kHeadForm = MODE == 2 && ST == kStWt && sizeof(T) == 1;
+    int64_t first_block = blockIdx.x;
+    if constexpr (kHeadForm) {
+        if (align_lines & 2) first_block = step_block(kStepOrderXcdFwd, blockIdx.x, gridDim.x);
+    }
+  for (int64_t wave = first_block * (blockDim.x / kWave) + wib; wave * EPW < B; wave += wave_stride) {
     const int64_t b0 = wave * EPW;
     const int nenv = (int)((B - b0) < EPW ? (B - b0) : EPW);
 
@@ -301,7 +309,7 @@ __global__ __launch_bounds__(256) void k_maxcut_step(const T* __restrict__ xin, 
             // the wait) whenever this block or its register pressure changes.
             unsigned char* region = smem + (size_t)wib * ((size_t)EPW * N * sizeof(T) + kStepPad);
             const int h_src = (int)((reinterpret_cast<uintptr_t>(src) >> 4) & 7), h_dst = (int)((reinterpret_cast<uintptr_t>(dst) >> 4) & 7);
-            const int h_in = align_lines ? h_src : 0, h_out = align_lines ? h_dst : 0;
+            const int h_in = (align_lines & 1) ? h_src : 0, h_out = (align_lines & 1) ? h_dst : 0;
             V* region_v = reinterpret_cast<V*>(region);
             V* stage_v = region_v + h_in;
             T* stage = reinterpret_cast<T*>(stage_v);
@@ -563,7 +571,8 @@ __global__ __launch_bounds__(256) void k_maxcut_step(const T* __restrict__ xin, 
 // for what such a call cannot need: the loop over runs, the short run and its element tail, the gather's loop for long rows, the
 // cur / done stores; indices inside a run are 32-bit (a staged run fits the LDS).  It is tools/ceilings/ring_step_ladder.hip's rung i
 // with K4's arguments.  Any other call runs k_maxcut_step.  The INVARIANT of the hand-issued loads (see there) holds here too.
-template <int EPW>
+// ORDER: the block order of rls_step_plan.h (round 10: xcd-fwd is the ladder's rung `i xcd-fwd`).
+template <int EPW, int ORDER>
 __global__ __launch_bounds__(256) void k_maxcut_step_lean(const uint8_t* __restrict__ xin, uint8_t* __restrict__ xout, int64_t B, int N,
                                                           const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                           const int64_t* __restrict__ action, int32_t* __restrict__ obj,
@@ -571,7 +580,7 @@ __global__ __launch_bounds__(256) void k_maxcut_step_lean(const uint8_t* __restr
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & (kWave - 1);
     const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
-    const int64_t b0 = ((int64_t)blockIdx.x * (blockDim.x / kWave) + wib) * EPW;
+    const int64_t b0 = (step_block(ORDER, blockIdx.x, gridDim.x) * (blockDim.x / kWave) + wib) * EPW;
     if (b0 >= B) return;                                    // (a last workgroup with fewer runs than waves)
     const int run = EPW * N, nvec = run >> 4;               // bytes and 16-byte vectors of a run
     const u32x4* src = reinterpret_cast<const u32x4*>(xin + b0 * N);
@@ -652,11 +661,12 @@ __global__ __launch_bounds__(256) void k_maxcut_step_lean(const uint8_t* __restr
 // (nontemporal stores), epw / wpb = 0: automatic, persist = -1 automatic | 0 one run per wave | k: k workgroup rounds per CU
 // resident, waves loop; chase = -1 automatic | 0 MODE 2 (stores after the last load) | 1 MODE 3 (stores chase the loads);
 // align = 0: load / store instructions start where the run starts (before round 4's fix); wt = -1 automatic | 0 | 1 (write-through
-// stores where the stores are not nontemporal; staged forms only)
-struct StepKnobs { int nts, epw, wpb, persist, chase, align, wt; };
+// stores where the stores are not nontemporal; staged forms only); order = -1 automatic | 0 forward | 1 xcd-fwd (rls_step_plan.h;
+// the write-through MODE 2 form on 1-byte rows with a one-shot grid only: every other form walks forward whatever the knob says)
+struct StepKnobs { int nts, epw, wpb, persist, chase, align, wt, order; };
 static StepKnobs step_knobs() {
     return StepKnobs{(int)knob(KN_STEP_NTS, -1), (int)knob(KN_STEP_EPW, 0), (int)knob(KN_STEP_WPB, 0), (int)knob(KN_STEP_PERSIST, -1),
-                     (int)knob(KN_STEP_CHASE, -1), (int)knob(KN_STEP_ALIGN, 1), (int)knob(KN_STEP_WT, -1)};
+                     (int)knob(KN_STEP_CHASE, -1), (int)knob(KN_STEP_ALIGN, 1), (int)knob(KN_STEP_WT, -1), (int)knob(KN_STEP_ORDER, -1)};
 }
 
 }  // namespace rls
@@ -736,6 +746,16 @@ extern "C" int rls_maxcut_step(const rls_graph* g, const void* x_in, void* x_out
     const bool nts = knobs.nts >= 0 ? knobs.nts != 0 : ((size_t)B * N * spin_bytes > ((size_t)256 << 20));
     // write-through in place of plain stores: MODE 2 by default (measured: tools/ceilings/ring_copy.hip, bench.py); MODE 3 when forced
     const bool wt = !nts && (knobs.wt > 0 || (knobs.wt < 0 && !chase));
+    // block order of the headline's form on a one-shot grid: xcd-fwd (rls_step_plan.h).  Round 10, tools/ceilings/ring_step_ladder.hip at
+    // the G22 shape (profiles/r10_step_ladder.txt): the bare ring copy 38.21 -> 37.26 us, with the action / reward traffic 38.87 ->
+    // 38.13, with obj 39.48 -> 38.56, the whole step (rung i) 39.46 -> 38.99, spreads <= 0.09.  Measured beside it and NOT taken
+    // (profiles/r10_ring_ceiling.txt): the six LDS-DMA policies never timed before (only the nt bit matters: 38.4 us with it, 44.6 -
+    // 48.2 without, sc0 / sc1 change nothing beside nt), nontemporal obj / reward stores (+0.06), a share of the runs stored
+    // nontemporal (+2.8 .. +6.4 us); us per MB falls steadily from 0.5 to 1.25 x this slot size: no Infinity Cache knee at 131 MB
+    const bool one_shot = nblocks == ceil_div(ceil_div(B, epw), waves_per_block);
+    const bool head_form = staged && wt && !chase && spin_bytes == 1;
+    const int order = head_form && one_shot && (knobs.order < 0 || knobs.order == kStepOrderXcdFwd) ? kStepOrderXcdFwd : kStepOrderFwd;
+    const int head_flags = (knobs.align ? 1 : 0) | (order == kStepOrderXcdFwd ? 2 : 0);   // k_maxcut_step's align_lines in the headline's form
 
 #define LAUNCH_STEP_E(T, EPW, MODE, EMIT, VEC, NTL, ST)                                                        \
     do {                                                                                                       \
@@ -743,7 +763,8 @@ extern "C" int rls_maxcut_step(const rls_graph* g, const void* x_in, void* x_out
         if (lds > 64 * 1024)                                                                                   \
             ensure_dyn_lds((const void*)kern, lds); \
         hipLaunchKernelGGL(kern, grid, block, lds, s, (const T*)x_in, (T*)x_out, B, N, g->rowptr, g->col, g->wgt, \
-                           action, obj, reward, cur, done, done_value, knobs.align);                           \
+                           action, obj, reward, cur, done, done_value,                                         \
+                           (MODE == 2 && ST == kStWt && sizeof(T) == 1) ? head_flags : knobs.align);           \
     } while (0)
 #define LAUNCH_STEP(T, MODE, EMIT, VEC, NTL, ST)                            \
     do {                                                                    \
@@ -769,11 +790,17 @@ extern "C" int rls_maxcut_step(const rls_graph* g, const void* x_in, void* x_out
     // one-shot grid, every run full, no cur / done, no row longer than a wave.  Round 9, interleaved A/B at the G22 shape
     // (profiles/r09_bench_ab.txt): plain bench.py 40.13 / 40.15 -> 39.12 / 39.10 us, --steps 20 40.48 .. 40.75 -> 39.57 .. 39.61; the
     // new gather and flip inside k_maxcut_step alone gave 0.4 of that 1.0 us (DESIGN_HISTORY.md section 13)
-    const bool lean = staged && wt && !chase && spin_bytes == 1 && (epw == 1 || epw == 2 || epw == 4 || epw == 8) && B % epw == 0 &&
-                      !cur && !done && g->max_degree <= kWave && nblocks == ceil_div(ceil_div(B, epw), waves_per_block);
+    // Round 10, with the block order xcd-fwd (above), interleaved A/B at the G22 shape (profiles/r10_bench_ab.txt): plain bench.py 39.15 /
+    // 39.18 -> 38.26 / 38.10 us, --steps 20 39.55 .. 39.79 -> 38.58 .. 38.96 (DESIGN_HISTORY.md section 14)
+    const bool lean = head_form && (epw == 1 || epw == 2 || epw == 4 || epw == 8) && B % epw == 0 && !cur && !done &&
+                      g->max_degree <= kWave && one_shot;
     if (lean) {
-        void (*kern)(const uint8_t*, uint8_t*, int64_t, int, const int32_t*, const int32_t*, const int64_t*, int32_t*, float*, int) =
-            epw == 1 ? k_maxcut_step_lean<1> : epw == 2 ? k_maxcut_step_lean<2> : epw == 8 ? k_maxcut_step_lean<8> : k_maxcut_step_lean<4>;
+        typedef void (*LeanFn)(const uint8_t*, uint8_t*, int64_t, int, const int32_t*, const int32_t*, const int64_t*, int32_t*, float*, int);
+        const LeanFn fwd = epw == 1 ? k_maxcut_step_lean<1, kStepOrderFwd> : epw == 2 ? k_maxcut_step_lean<2, kStepOrderFwd>
+                         : epw == 8 ? k_maxcut_step_lean<8, kStepOrderFwd> : k_maxcut_step_lean<4, kStepOrderFwd>;
+        const LeanFn xcd = epw == 1 ? k_maxcut_step_lean<1, kStepOrderXcdFwd> : epw == 2 ? k_maxcut_step_lean<2, kStepOrderXcdFwd>
+                         : epw == 8 ? k_maxcut_step_lean<8, kStepOrderXcdFwd> : k_maxcut_step_lean<4, kStepOrderXcdFwd>;
+        const LeanFn kern = order == kStepOrderXcdFwd ? xcd : fwd;
         if (lds > 64 * 1024) ensure_dyn_lds((const void*)kern, lds);
         hipLaunchKernelGGL(kern, grid, block, lds, s, (const uint8_t*)x_in, (uint8_t*)x_out, B, (int)N, g->rowptr, g->col, action, obj,
                            reward, knobs.align);

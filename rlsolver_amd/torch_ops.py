@@ -61,7 +61,7 @@ DEVICE_ENTRY_POINTS = [
 # declared in the header but not device work: host-side schedule builders and queries (plain C calls, no op)
 HOST_ENTRY_POINTS = [
     "version", "last_error_string", "device_count", "graph_sweep_schedule", "graph_sweep_levels", "graph_ell", "graph_sweep_batches",
-    "mcpg_visit_levels", "maxcut_local_search_supported", "mcpg_local_search_levels_supported", "qubo_local_search_supported", "maxcut_ls_rounds_supported", "maxcut_ls_scratch_bytes", "maxcut_ls_slices", "maxcut_node_stats_form", "maxcut_launch_plan", "mcpg_metro_max_rounds", "mcpg_metro_scratch_bytes", "isco_maxcut_scratch_bytes", "pisco_scratch_bytes", "tsp_tables8_bytes", "tsp_launch_form",
+    "mcpg_visit_levels", "maxcut_local_search_supported", "mcpg_local_search_levels_supported", "qubo_local_search_supported", "maxcut_ls_rounds_supported", "maxcut_ls_scratch_bytes", "maxcut_ls_slices", "maxcut_node_stats_form", "maxcut_launch_plan", "maxcut_step_block", "mcpg_metro_max_rounds", "mcpg_metro_scratch_bytes", "isco_maxcut_scratch_bytes", "pisco_scratch_bytes", "tsp_tables8_bytes", "tsp_launch_form",
     "tuning_set", "tuning_unset", "tuning_get", "tuning_name", "maxsat_visit_levels", "maxsat_local_search_supported", "cheeger_local_search_supported", "maxcut_edge_local_search_supported", "mimo_local_search_supported", "sub_set_sampling_supported", "s2vppo_launch_plan",
     "isco_launch_plan", "maxcut_ls_launch_plan", "tsp_3opt_launch_form", "tsp_grow_launch_form",
 ]

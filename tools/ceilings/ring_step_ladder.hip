@@ -17,18 +17,26 @@
 //        gather has read, no read-modify-write, no wait, no barrier: measured against e
 //   j  i with the wave's obj / reward stores write-through (sc1)
 //   k  i with the store loop reading 8 pieces of the run from LDS before it stores the first: measured against i
+// Round 10 adds, each measured against the rung it is named after:
+//   a / b / c / i  xcd-fwd   the same rung with the block order xcd-fwd (see xcd_fwd_block): under round-robin placement one XCD owns a
+//                            contiguous eighth of the batch, so every obj / reward line is whole in one L2
+//   i  aux A                 rung i with the LDS-DMA cache-policy immediate A (sc0 = 1, nt = 2, sc1 = 16; rung i itself is aux 2)
+//   i  side-band nt          rung i with the wave's obj / reward stores nontemporal
 // (rungs f - k are a kernel of their own, k_rung_wg; `vs below` of i is against e: the rungs a - e stay the code round 8 measured)
 // The graph is synthetic: N nodes of degree 20, node i's row = i + 1 + 97 j mod N, j = 0..19 (N is refused where two of these
 // coincide or one is i itself).  16 random action vectors, pass k takes vector k % 16.  All rungs interleaved in one process, 5 rounds
 // of 200 passes; the spread of a rung is the max - min of its five rounds.  Before it is timed, every rung's pass 0 is checked against the host: the output slot is the input (rungs d, e: with
 // each env's action byte flipped), reward and obj's change are what the rung is meant to compute -- a rung that dropped work fails.
 // Build: hipcc --offload-arch=gfx950 -O3 -o /tmp/ring_step_ladder tools/ceilings/ring_step_ladder.hip
-// Run:   /tmp/ring_step_ladder [B N]     (default: the G22 shape 65536 2000; B a multiple of 4, 4 N a multiple of 16)
+// Run:   /tmp/ring_step_ladder [B N [tags]]   (default: the G22 shape 65536 2000; B a multiple of 4, 4 N a multiple of 16; tags: a
+//        comma-separated list of the rungs to run, by the tag in front of each row, e.g. a,i,i-sbnt -- the rung a row is measured
+//        against is run with it)
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -40,14 +48,22 @@ __device__ __forceinline__ void store16_wt(u32x4* p, u32x4 v) {
     asm volatile("global_store_dwordx4 %0, %1, off sc1\n s_nop 1" :: "v"(p), "v"(v) : "memory");
 }
 
-template <int RUNG>   // 0 .. 4 = a .. e
+// xcd-fwd: block b -> virtual block; blocks with equal b % 8 (one XCD under round-robin placement) get one contiguous range, in
+// order.  A bijection on [0, nvb) for every nvb: the first nvb % 8 classes hold one block more.  Placement is a speed assumption only.
+__host__ __device__ inline int64_t xcd_fwd_block(int64_t b, int64_t nvb) {
+    const int64_t q = nvb / 8, r = nvb % 8, x = b % 8;
+    return x * q + (x < r ? x : r) + b / 8;
+}
+
+template <int RUNG, int ORDER = 0>   // 0 .. 4 = a .. e; ORDER 1: xcd-fwd
 __global__ __launch_bounds__(256) void k_rung(const unsigned char* __restrict__ xin, unsigned char* __restrict__ xout, int64_t B, int64_t N,
                                               const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                               const int64_t* __restrict__ action, int32_t* __restrict__ obj, float* __restrict__ reward) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & (kWave - 1);
     const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
-    const int64_t b0 = ((int64_t)blockIdx.x * kWpb + wib) * kEpw;
+    const int64_t vblock = ORDER ? xcd_fwd_block(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;
+    const int64_t b0 = (vblock * kWpb + wib) * kEpw;
     if (b0 >= B) return;
     const int nenv = (int)((B - b0) < kEpw ? (B - b0) : kEpw);
     const int64_t nvec = (int64_t)nenv * N / 16;
@@ -169,7 +185,7 @@ __device__ __forceinline__ u32x4 flip_byte(u32x4 v, int word, int sh) {   // log
 constexpr int kMailbox = kWpb * kEpw * 8 + 16;
 constexpr int kStoreBatch = 8;   // rung k: 1 KB pieces read from LDS before the first is stored
 
-template <int RUNG>   // 5 .. 10 = f .. k
+template <int RUNG, int AUX = 2, int ORDER = 0, bool SBNT = false>   // 5 .. 10 = f .. k; AUX: LDS-DMA policy; ORDER 1: xcd-fwd; SBNT: obj / reward stored nt
 __global__ __launch_bounds__(256) void k_rung_wg(const unsigned char* __restrict__ xin, unsigned char* __restrict__ xout, int64_t B, int64_t N,
                                                  const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                  const int64_t* __restrict__ action, int32_t* __restrict__ obj, float* __restrict__ reward) {
@@ -187,7 +203,7 @@ __global__ __launch_bounds__(256) void k_rung_wg(const unsigned char* __restrict
         if (threadIdx.x == 0) *mb_arrived = 0;
         __syncthreads();                  // before any load is issued; a wave without a run leaves only behind it
     }
-    const int64_t wg_b0 = (int64_t)blockIdx.x * kWpb * kEpw;
+    const int64_t wg_b0 = (ORDER ? xcd_fwd_block(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x) * kWpb * kEpw;
     const int64_t b0 = wg_b0 + (int64_t)wib * kEpw;
     if (b0 >= B) return;
     const int64_t wg_runs = (B - wg_b0 + kEpw - 1) / kEpw;
@@ -224,7 +240,7 @@ __global__ __launch_bounds__(256) void k_rung_wg(const unsigned char* __restrict
         const int64_t i = s0 + lane - h_in;
         if (i >= 0 && i < nvec)
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + i),
-                                             (__attribute__((address_space(3))) void*)(region + s0), 16, 0, 2);
+                                             (__attribute__((address_space(3))) void*)(region + s0), 16, 0, AUX);
     }
     int r0[kEpw], deg[kEpw], nb[kEpw];
 #pragma unroll
@@ -294,6 +310,9 @@ __global__ __launch_bounds__(256) void k_rung_wg(const unsigned char* __restrict
             if constexpr (SC1) {
                 asm volatile("global_store_dword %0, %1, off sc1" :: "v"(obj + b0 + lane), "v"(v) : "memory");
                 asm volatile("global_store_dword %0, %1, off sc1" :: "v"(reward + b0 + lane), "v"(r) : "memory");
+            } else if constexpr (SBNT) {
+                __builtin_nontemporal_store(v, obj + b0 + lane);
+                __builtin_nontemporal_store(r, reward + b0 + lane);
             } else {
                 obj[b0 + lane] = v;
                 reward[b0 + lane] = r;
@@ -401,20 +420,48 @@ int main(int argc, char** argv) {
                         "than i, and 4 staged runs within 160 KB of LDS\n");
         return 1;
     }
-    constexpr int NR = 11;
-    const KernFn K[NR] = {k_rung<0>, k_rung<1>, k_rung<2>, k_rung<3>, k_rung<4>, k_rung_wg<5>, k_rung_wg<6>, k_rung_wg<7>, k_rung_wg<8>,
-                          k_rung_wg<9>, k_rung_wg<10>};
-    const char* NAME[NR] = {"a  copy only", "b  + action read, reward write", "c  + obj read-modify-write after the run",
-                           "d  + rowptr -> col chain, gather, flip after the run (serial per env)", "e  the work of d, operands requested beside the run",
-                            "f  e, obj / reward leave once per workgroup (LDS mailbox, last arriver stores)",
-                            "g  f, one wait for all gather reads, flip in registers in the store loop",
-                            "h  g, the publisher's stores write-through (sc1)",
-                            "i  e, one wait for all gather reads, flip = one LDS write of the byte read (vs e)",
-                            "j  i, the wave's obj / reward stores write-through (sc1)",
-                            "k  i, the store loop reads 8 pieces from LDS before it stores the first (vs i)"};
-    auto lds_of = [&](int r) { return r >= 5 && r <= 7 ? lds + kMailbox : lds; };
-    const int BELOW[NR] = {0, 0, 1, 2, 3, 4, 5, 6, 4, 8, 8};       // the rung each one is measured against
-    for (auto k : K) CK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    // kind: what pass 0 must have computed -- 0 copy, 1 + reward, 2 + obj, 3 the gain and the flip
+    struct Rung { const char* tag; const char* name; KernFn fn; int kind; bool mailbox; const char* below; };
+    const std::vector<Rung> ALL = {
+        {"a", "a  copy only", k_rung<0>, 0, false, "a"},
+        {"b", "b  + action read, reward write", k_rung<1>, 1, false, "a"},
+        {"c", "c  + obj read-modify-write after the run", k_rung<2>, 2, false, "b"},
+        {"d", "d  + rowptr -> col chain, gather, flip after the run (serial per env)", k_rung<3>, 3, false, "c"},
+        {"e", "e  the work of d, operands requested beside the run", k_rung<4>, 3, false, "d"},
+        {"f", "f  e, obj / reward leave once per workgroup (LDS mailbox, last arriver stores)", k_rung_wg<5>, 3, true, "e"},
+        {"g", "g  f, one wait for all gather reads, flip in registers in the store loop", k_rung_wg<6>, 3, true, "f"},
+        {"h", "h  g, the publisher's stores write-through (sc1)", k_rung_wg<7>, 3, true, "g"},
+        {"i", "i  e, one wait for all gather reads, flip = one LDS write of the byte read (vs e)", k_rung_wg<8>, 3, false, "e"},
+        {"j", "j  i, the wave's obj / reward stores write-through (sc1)", k_rung_wg<9>, 3, false, "i"},
+        {"k", "k  i, the store loop reads 8 pieces from LDS before it stores the first (vs i)", k_rung_wg<10>, 3, false, "i"},
+        {"a-x", "a  xcd-fwd (vs a)", k_rung<0, 1>, 0, false, "a"},
+        {"b-x", "b  xcd-fwd (vs b)", k_rung<1, 1>, 1, false, "b"},
+        {"c-x", "c  xcd-fwd (vs c)", k_rung<2, 1>, 2, false, "c"},
+        {"i-x", "i  xcd-fwd (vs i)", k_rung_wg<8, 2, 1>, 3, false, "i"},
+        {"i-aux0", "i  aux 0: default policy (vs i)", k_rung_wg<8, 0>, 3, false, "i"},
+        {"i-aux1", "i  aux 1: sc0 (vs i)", k_rung_wg<8, 1>, 3, false, "i"},
+        {"i-aux3", "i  aux 3: sc0 nt (vs i)", k_rung_wg<8, 3>, 3, false, "i"},
+        {"i-aux16", "i  aux 16: sc1 (vs i)", k_rung_wg<8, 16>, 3, false, "i"},
+        {"i-aux17", "i  aux 17: sc0 sc1 (vs i)", k_rung_wg<8, 17>, 3, false, "i"},
+        {"i-aux18", "i  aux 18: nt sc1 (vs i)", k_rung_wg<8, 18>, 3, false, "i"},
+        {"i-aux19", "i  aux 19: sc0 nt sc1 (vs i)", k_rung_wg<8, 19>, 3, false, "i"},
+        {"i-sbnt", "i  side-band nt: obj / reward stored nontemporal (vs i)", k_rung_wg<8, 2, 0, true>, 3, false, "i"},
+    };
+    std::vector<Rung> R;
+    {
+        const std::string want = argc >= 4 ? std::string(",") + argv[3] + "," : "";
+        auto asked = [&](const char* tag) { return want.empty() || want.find(std::string(",") + tag + ",") != std::string::npos; };
+        for (const Rung& r : ALL) {
+            bool take = asked(r.tag);
+            for (const Rung& o : ALL) take = take || (asked(o.tag) && std::string(o.below) == r.tag);
+            if (take) R.push_back(r);
+        }
+        if (R.empty()) { fprintf(stderr, "no rung has one of the tags %s\n", argv[3]); return 1; }
+    }
+    const int NR = (int)R.size();
+    auto lds_of = [&](int r) { return R[r].mailbox ? lds + kMailbox : lds; };
+    auto below_of = [&](int r) { for (int o = 0; o < NR; ++o) if (std::string(R[o].tag) == R[r].below) return o; return r; };
+    for (const Rung& r : R) CK(hipFuncSetAttribute((const void*)r.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 
     // graph: node i's row = i + 1 + 97 j mod N, j = 0..19 (distinct and never i itself: checked above)
     std::vector<int32_t> h_rowptr(N + 1), h_col((size_t)N * kDeg);
@@ -446,7 +493,7 @@ int main(int argc, char** argv) {
         std::vector<float> h_rew(B);
         for (int r = 0; r < NR; ++r) {
             CK(hipMemset(obj, 0, B * 4)); CK(hipMemset(reward, 0xff, B * 4)); CK(hipMemset(slot[1], 2, bytes));
-            hipLaunchKernelGGL(K[r], dim3(grid), dim3(kWpb * kWave), lds_of(r), 0, slot[0], slot[1], B, N, rowptr, col, action, obj, reward);
+            hipLaunchKernelGGL(R[r].fn, dim3(grid), dim3(kWpb * kWave), lds_of(r), 0, slot[0], slot[1], B, N, rowptr, col, action, obj, reward);
             CK(hipDeviceSynchronize());
             CK(hipMemcpy(h_out.data(), slot[1], bytes, hipMemcpyDeviceToHost));
             CK(hipMemcpy(h_obj.data(), obj, B * 4, hipMemcpyDeviceToHost));
@@ -456,32 +503,33 @@ int main(int argc, char** argv) {
                 const int64_t a = h_act[b];
                 const unsigned char* row = &h_in[b * N];
                 int want = 0;
-                if (r >= 3) {
+                const int kind = R[r].kind;
+                if (kind >= 3) {
                     int cut = 0;
                     for (int j = 0; j < kDeg; ++j) cut += row[h_col[a * kDeg + j]] != row[a];
                     want = kDeg - 2 * cut;
-                } else if (r >= 1) {
+                } else if (kind >= 1) {
                     want = (int)(a & 1) * 2 - 1;
                 }
                 for (int64_t i = 0; i < N; ++i) {
-                    const unsigned char w = (r >= 3 && i == a) ? (row[i] == 0 ? 1 : 0) : row[i];
+                    const unsigned char w = (kind >= 3 && i == a) ? (row[i] == 0 ? 1 : 0) : row[i];
                     bad_bytes += h_out[b * N + i] != w;
                 }
-                if (r >= 1 && h_rew[b] != (float)want) ++bad_env;
-                if (h_obj[b] != (r >= 2 ? want : 0)) ++bad_env;
+                if (kind >= 1 && h_rew[b] != (float)want) ++bad_env;
+                if (h_obj[b] != (kind >= 2 ? want : 0)) ++bad_env;
             }
-            if (bad_bytes || bad_env) { fprintf(stderr, "rung %c: %lld wrong output bytes, %lld wrong reward / obj entries\n", 'a' + r, bad_bytes, bad_env); return 1; }
+            if (bad_bytes || bad_env) { fprintf(stderr, "rung %s: %lld wrong output bytes, %lld wrong reward / obj entries\n", R[r].tag, bad_bytes, bad_env); return 1; }
         }
         printf("pass 0 of every rung equals the host's result (output slot, reward, obj)\n");
         CK(hipMemset(obj, 0, B * 4));
     }
     const int passes = 200;
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-    std::vector<float> us[NR];
+    std::vector<std::vector<float>> us(NR);
     for (int rep = 0; rep < 5; ++rep)
         for (int r = 0; r < NR; ++r) {
             auto pass = [&](int k) {
-                hipLaunchKernelGGL(K[r], dim3(grid), dim3(kWpb * kWave), lds_of(r), 0, slot[k % S], slot[(k + 1) % S], B, N, rowptr, col,
+                hipLaunchKernelGGL(R[r].fn, dim3(grid), dim3(kWpb * kWave), lds_of(r), 0, slot[k % S], slot[(k + 1) % S], B, N, rowptr, col,
                                    action + (size_t)(k % NA) * B, obj, reward);
             };
             for (int k = 0; k < 16; ++k) pass(k);
@@ -495,17 +543,18 @@ int main(int argc, char** argv) {
         }
     printf("B = %lld, N = %lld bytes, EPW = %d, degree %d: slot %.1f MB, %u workgroups; %d passes per timing, 5 interleaved rounds\n",
            (long long)B, (long long)N, kEpw, kDeg, bytes / 1e6, grid, passes);
-    printf("%-78s %8s %8s %8s %9s %9s %7s %8s\n", "rung", "us min", "us med", "us max", "vs below", "vs a", "spread", "wg / CU");
-    float med[NR] = {0}, base = 0;
+    printf("%-8s %-78s %8s %8s %8s %9s %9s %7s %8s\n", "tag", "rung", "us min", "us med", "us max", "vs below", "vs a", "spread", "wg / CU");
+    std::vector<float> med(NR, 0.f);
+    float base = 0;
+    for (int r = 0; r < NR; ++r) { auto t = us[r]; std::sort(t.begin(), t.end()); med[r] = t[2]; }
     for (int r = 0; r < NR; ++r) {
         auto t = us[r];
         std::sort(t.begin(), t.end());
         if (r == 0) base = t[2];
         int per_cu = 0;     // resident workgroups per CU at this rung's LDS size
-        CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)K[r], kWpb * kWave, lds_of(r)));
-        printf("%-78s %8.2f %8.2f %8.2f %+9.2f %+9.2f %7.2f %8d\n", NAME[r], t[0], t[2], t[4], r ? t[2] - med[BELOW[r]] : 0.f, t[2] - base,
-               t[4] - t[0], per_cu);
-        med[r] = t[2];
+        CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)R[r].fn, kWpb * kWave, lds_of(r)));
+        printf("%-8s %-78s %8.2f %8.2f %8.2f %+9.2f %+9.2f %7.2f %8d\n", R[r].tag, R[r].name, t[0], t[2], t[4], t[2] - med[below_of(r)],
+               t[2] - base, t[4] - t[0], per_cu);
     }
     return 0;
 }
