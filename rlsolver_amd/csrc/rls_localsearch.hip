@@ -831,7 +831,7 @@ __global__ __launch_bounds__(W * kWave) void k_ls_apply_rounds32(uint8_t* __rest
         const uint32_t* mw = reinterpret_cast<const uint32_t*>(maskw + ((int64_t)r * tiles64 + (blockIdx.x >> 1)) * N) + (blockIdx.x & 1);
         for (int64_t n = threadIdx.x; n < N; n += W * kWave) words32[n] ^= mw[2 * n];
         __syncthreads();
-        int64_t total = block_sum_partials<W>(tile32_cut_count<P>(words32, eu, ev, E, lane, w, W), scratch, lane, w);
+        int64_t total = block_sum_partials<W>(tile_cut_count<P>(words32, eu, ev, E, lane, w, W), scratch, lane, w);
         if (halve) total >>= 1;
         const bool accept = valid && (total >= my_obj);          // update_xs_by_vs: vs1.ge(vs0)
         if (accept) my_obj = total;

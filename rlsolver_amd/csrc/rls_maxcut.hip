@@ -69,7 +69,7 @@ __global__ __launch_bounds__(W * kWave) void k_maxcut_obj32(const T* __restrict_
     unsigned char* stage = stage_off >= 0 ? smem + stage_off + w * kStageBytes : nullptr;
     tile32_load_bits<T, VEC>(x, B, N, b0, words32, lane, w, W, stage);
     __syncthreads();
-    const int64_t part = tile32_cut_count<P>(words32, eu, ev, E, lane, w, W);
+    const int64_t part = tile_cut_count<P>(words32, eu, ev, E, lane, w, W);
     int64_t total = block_sum_partials<W>(part, scratch, lane, w);
     if (halve) total >>= 1;
     if (w == 0 && lane < kHalf && b0 + lane < B) obj[b0 + lane] = total;
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(W * kWave) void k_maxcut_propose_accept32(uint8_t* 
         tile32_load_bits<uint8_t, VEC, true>(mask, B, N, b0, words32, lane, w, W, stage);
     }
     __syncthreads();
-    int64_t total = block_sum_partials<W>(tile32_cut_count<P>(words32, eu, ev, E, lane, w, W), scratch, lane, w);
+    int64_t total = block_sum_partials<W>(tile_cut_count<P>(words32, eu, ev, E, lane, w, W), scratch, lane, w);
     if (halve) total >>= 1;
     const int64_t b = b0 + (lane & (kHalf - 1));
     const bool accept = (b < B) && (total >= obj[b]);     // (block_sum_partials leaves lanes 32..63 with 0: they hold their env's verdict below)
@@ -276,9 +276,9 @@ __global__ __launch_bounds__(SW * kWave) void k_maxcut_greedy_sweep_levels32(
     unsigned char* stage = has_stage ? stages + (w % LW) * kStageBytes : nullptr;
     if (w < LW) tile32_load_bits<uint8_t, VEC>(x, B, N, b0, words32, lane, w, LW, stage);
     __syncthreads();
-    sweep32_tile_levels<SW>(words32, lvp, lv_data, G, N, lane, w);
+    sweep_tile_levels<SW>(words32, lvp, lv_data, G, N, lane, w);
     if (w < LW) tile32_store_bytes<VEC>(x, B, N, b0, words32, lane, w, LW, true, stage);   // (stores first: they drain under the count)
-    const int64_t after = block_sum_partials<SW>(tile32_cut_count<P>(words32, eu, ev, E, lane, w, SW), scratch, lane, w);
+    const int64_t after = block_sum_partials<SW>(tile_cut_count<P>(words32, eu, ev, E, lane, w, SW), scratch, lane, w);
     if (w == 0 && lane < kHalf && b0 + lane < B) obj[b0 + lane] = halve ? (after >> 1) : after;
 }
 
@@ -301,7 +301,7 @@ __global__ __launch_bounds__(kNarrowWaves * kWave) void k_maxcut_obj_n(const T* 
     const int64_t b0 = (int64_t)blockIdx.x * EN;
     tilen_load_bits<T, WT, VEC>(x, B, N, b0, words, lane, w, W);
     __syncthreads();
-    int64_t total = block_sum_partials<W>(tile32_cut_count<P, WT>(words, eu, ev, E, lane, w, W), scratch, lane, w);
+    int64_t total = block_sum_partials<W>(tile_cut_count<P>(words, eu, ev, E, lane, w, W), scratch, lane, w);
     if (halve) total >>= 1;
     if (w == 0 && lane < EN && b0 + lane < B) obj[b0 + lane] = total;
 }
@@ -328,7 +328,7 @@ __global__ __launch_bounds__(kNarrowWaves * kWave) void k_maxcut_propose_accept_
         tilen_load_bits<uint8_t, WT, VEC, true>(mask, B, N, b0, words, lane, w, W);
     }
     __syncthreads();
-    int64_t total = block_sum_partials<W>(tile32_cut_count<P, WT>(words, eu, ev, E, lane, w, W), scratch, lane, w);
+    int64_t total = block_sum_partials<W>(tile_cut_count<P>(words, eu, ev, E, lane, w, W), scratch, lane, w);
     if (halve) total >>= 1;
     const int64_t b = b0 + (lane % EN);
     const bool accept = (b < B) && (total >= obj[b]);     // (lanes >= E hold 0: they take their env's verdict below)
@@ -355,9 +355,9 @@ __global__ __launch_bounds__(kNarrowWaves * kWave) void k_maxcut_greedy_sweep_le
     for (int64_t i = threadIdx.x; i <= G; i += SW * kWave) lvp[i] = lv_ptr[i];
     tilen_load_bits<uint8_t, WT, VEC>(x, B, N, b0, words, lane, w, SW);
     __syncthreads();
-    sweep32_tile_levels<SW, WT>(words, lvp, lv_data, G, N, lane, w);
+    sweep_tile_levels<SW>(words, lvp, lv_data, G, N, lane, w);
     tilen_store_bytes<WT, VEC>(x, B, N, b0, words, lane, w, SW, true);
-    const int64_t after = block_sum_partials<SW>(tile32_cut_count<P, WT>(words, eu, ev, E, lane, w, SW), scratch, lane, w);
+    const int64_t after = block_sum_partials<SW>(tile_cut_count<P>(words, eu, ev, E, lane, w, SW), scratch, lane, w);
     if (w == 0 && lane < EN && b0 + lane < B) obj[b0 + lane] = halve ? (after >> 1) : after;
 }
 
@@ -1040,13 +1040,13 @@ __global__ __launch_bounds__(kNsWaves * kWave) void k_node_stats_bits32(const ui
 #pragma unroll
                         for (int q = 0; q < 8; ++q) d[q] = (uint32_t)words32[nb[q]] ^ own;
                         uint32_t twosA, twosB, foursA, foursB, carry;
-                        csa32(twosA, ones, ones, d[0], d[1]);
-                        csa32(twosB, ones, ones, d[2], d[3]);
-                        csa32(foursA, twos, twos, twosA, twosB);
-                        csa32(twosA, ones, ones, d[4], d[5]);
-                        csa32(twosB, ones, ones, d[6], d[7]);
-                        csa32(foursB, twos, twos, twosA, twosB);
-                        csa32(carry, fours, fours, foursA, foursB);
+                        csa(twosA, ones, ones, d[0], d[1]);
+                        csa(twosB, ones, ones, d[2], d[3]);
+                        csa(foursA, twos, twos, twosA, twosB);
+                        csa(twosA, ones, ones, d[4], d[5]);
+                        csa(twosB, ones, ones, d[6], d[7]);
+                        csa(foursB, twos, twos, twosA, twosB);
+                        csa(carry, fours, fours, foursA, foursB);
 #pragma unroll
                         for (int p = 0; p < NCP; ++p) {
                             if (p < 5 || p < ncp) {
@@ -1136,13 +1136,13 @@ __global__ __launch_bounds__(kNsWaves * kWave) void k_node_stats_bits32(const ui
 #pragma unroll
             for (int q = 0; q < 8; ++q) d[q] = (uint32_t)words32[nb[q]] ^ own;
             uint32_t twosA, twosB, foursA, foursB, carry;
-            csa32(twosA, ones, ones, d[0], d[1]);
-            csa32(twosB, ones, ones, d[2], d[3]);
-            csa32(foursA, twos, twos, twosA, twosB);
-            csa32(twosA, ones, ones, d[4], d[5]);
-            csa32(twosB, ones, ones, d[6], d[7]);
-            csa32(foursB, twos, twos, twosA, twosB);
-            csa32(carry, fours, fours, foursA, foursB);
+            csa(twosA, ones, ones, d[0], d[1]);
+            csa(twosB, ones, ones, d[2], d[3]);
+            csa(foursA, twos, twos, twosA, twosB);
+            csa(twosA, ones, ones, d[4], d[5]);
+            csa(twosB, ones, ones, d[6], d[7]);
+            csa(foursB, twos, twos, twosA, twosB);
+            csa(carry, fours, fours, foursA, foursB);
 #pragma unroll
             for (int p = 0; p < NCP; ++p) {
                 if (p < 5 || p < ncp) {

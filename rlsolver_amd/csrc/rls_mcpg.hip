@@ -578,36 +578,9 @@ __global__ __launch_bounds__(kK7Waves * kWave) void k_mcpg_local_search_stream(
 constexpr int kLvWaves = 16;      // f32 / uint8 node-major surface: 16 waves mostly to move the tile
 constexpr int kLvWavesPacked = 8; // bit-packed chains: the tile is a straight copy; 8 waves, two workgroups per CU at N = 10^4
 
-// 8 words into a (ones, twos, fours, c[0..NC-1] = planes 3..) vertical counter.  NC follows the group's number of
-// rounds (a count <= 7 never carries out of `fours`, <= 15 needs one more plane, ...): the ripple is 4 VALU per plane.
-template <int NC>
-__device__ __forceinline__ void lv_add8(const uint64_t (&d)[8], uint64_t& ones, uint64_t& twos, uint64_t& fours,
-                                        uint64_t (&c)[5]) {
-    uint64_t twosA, twosB, foursA, foursB, carry;
-    csa(twosA, ones, ones, d[0], d[1]);
-    csa(twosB, ones, ones, d[2], d[3]);
-    csa(foursA, twos, twos, twosA, twosB);
-    csa(twosA, ones, ones, d[4], d[5]);
-    csa(twosB, ones, ones, d[6], d[7]);
-    csa(foursB, twos, twos, twosA, twosB);
-    csa(carry, fours, fours, foursA, foursB);
-#pragma unroll
-    for (int p = 0; p < NC; ++p) {
-        const uint64_t t = c[p] & carry;
-        c[p] ^= carry;
-        carry = t;
-    }
-}
-
-// rls_tile.h: lv_merge_planes, on nine planes
-template <int X>
-__device__ __forceinline__ void lv_merge_planes9(uint64_t (&pl)[9], uint64_t take) {
-    uint64_t carry = 0;
-#pragma unroll
-    for (int p = 0; p < 9; ++p) csa(carry, pl[p], pl[p], lv_lane_xor<X>(pl[p]) & take, carry);
-}
-
-// The same eight words at weight TWO: they enter at the `twos` plane (pass 0 counts a not-yet-visited neighbour twice, C = cV + 2 cF:
+// The vertical counter is (ones, twos, fours, c[0..NC-1] = planes 3..), fed eight words at a time by add8<NC> (rls_planes.h); NC
+// follows the group's number of rounds.
+// Eight words at weight TWO: they enter at the `twos` plane (pass 0 counts a not-yet-visited neighbour twice, C = cV + 2 cF:
 // one counter takes both kinds, each at its own weight -- a second set of planes for cF and the plane-by-plane sum at the end cost
 // 16 registers and NP more adders).  NCW = planes above `fours` (>= 1).
 template <int NCW>
@@ -655,12 +628,12 @@ __device__ __forceinline__ void lv_count_block(const uint32_t (&e)[8], bool pass
             df[q] = d[q] & fm;
             dv[q] = d[q] & ~fm;
         }
-        lv_add8<NCW>(dv, vo, vt, vf, vc);
+        add8<NCW>(dv, vo, vt, vf, vc);
         lv_add8_x2<NCW>(df, vt, vf, vc);
     } else {
 #pragma unroll
         for (int q = 0; q < 8; ++q) d[q] = lds_word_at(e[q]);   // (the flag-free copy of the table)
-        lv_add8<NC>(d, vo, vt, vf, vc);
+        add8<NC>(d, vo, vt, vf, vc);
     }
 }
 
@@ -701,9 +674,9 @@ __device__ __forceinline__ void lv_node_group(const int32_t* __restrict__ blk, i
         // (a lane holds <= 64 entries: its own count fits the 8 planes, C <= 128; the node's -- up to 8 lanes, degree <= 128,
         // C <= 256 in pass 0 -- needs the ninth)
         uint64_t pv[9] = {vo, vt, vf, vc[0], vc[1], vc[2], vc[3], vc[4], 0};
-        lv_merge_planes9<1>(pv, 0ull - (uint64_t)(lcode >= 1u));
-        if (gl > 1) lv_merge_planes9<2>(pv, 0ull - (uint64_t)(lcode >= 2u));
-        if (gl > 2) lv_merge_planes9<4>(pv, 0ull - (uint64_t)(lcode >= 3u));
+        lv_merge_planes<1>(pv, 0ull - (uint64_t)(lcode >= 1u));
+        if (gl > 1) lv_merge_planes<2>(pv, 0ull - (uint64_t)(lcode >= 2u));
+        if (gl > 2) lv_merge_planes<4>(pv, 0ull - (uint64_t)(lcode >= 3u));
         nw = lv_le_const_x2<9, 9>(pv, ~coin, S);
         return;
     }
@@ -874,7 +847,7 @@ __global__ __launch_bounds__(W * kWave, 4) void k_mcpg_local_search_levels(
                 const uint32_t lcode = (h0 >> 28) & 3u;
                 // new bit = [C < K] | ([C == K] & tie & coin) with K = ceil(S / 2), tie = S even (S = the degree; + the not-yet-
                 // visited neighbours in pass 0)  <=>  2 C + !coin <= S: ONE bit-sliced "<= constant" on the counter shifted up a
-                // plane with the coin below it (carry chain of D + ~S, rls_tile.h) -- the scan that kept "smaller so far" and
+                // plane with the coin below it (carry chain of D + ~S, rls_planes.h) -- the scan that kept "smaller so far" and
                 // "equal so far" per plane cost ~2.5x the instructions
                 const uint32_t S = 2u * K - 1u + ((pass0 ? h1 : h0) >> 31);
                 uint64_t nw;

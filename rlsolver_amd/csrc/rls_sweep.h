@@ -145,10 +145,18 @@ __device__ __forceinline__ int64_t sweep_tile_batched(uint64_t* words, const int
 // k % W, which loads its NEXT group's header and first rounds before it waits at the level barrier, so the L2
 // latency of the schedule hides behind the other waves' levels.  lvp = LDS copy of lv_ptr (G + 1 entries).
 // words[N] must be 0 (idle lanes point there).  The caller recounts the objective afterwards.
-template <int NP>
-__device__ __forceinline__ uint64_t lv_count_le(const uint64_t (&pl)[8], uint32_t thr) {
-    // mask of envs whose NP-bit vertical counter is <= thr (per lane): the carry chain of c + ~thr (rls_tile.h: lv_le_const)
-    return lv_le_const<NP, 8>(pl, thr);
+//
+// One body for every tile width.  WT = the tile's LDS word (uint64_t: 64 envs; uint32_t: the half tile; uint16_t / uint8_t: the narrow
+// tiles of rls_tile32.h), PW = plane_word_t<WT> its plane word (rls_planes.h).  The SAME schedule serves them all: its entries are
+// byte offsets of 64-bit words (node * 8), shifted down to the width at the read; a group costs the same instructions per plane and,
+// on 32-bit planes, HALF as many planes' halves.  Only the hub step differs by width (sweep_hub_flips).
+
+// the tile word of the node whose 64-bit-word byte offset is `nb` (the schedule's entries): the tile sits at LDS address 0
+template <typename WT>
+__device__ __forceinline__ plane_word_t<WT> sweep_word_at(uint32_t nb) {
+    typedef const WT __attribute__((address_space(3))) lds_cwt;
+    constexpr int SH = sizeof(WT) == 8 ? 0 : (sizeof(WT) == 4 ? 1 : (sizeof(WT) == 2 ? 2 : 3));
+    return (plane_word_t<WT>)*(lds_cwt*)(uintptr_t)(nb >> SH);
 }
 
 // One group of the level schedule: vertical counters of "neighbour differs" over its rounds (entries = LDS byte
@@ -158,40 +166,23 @@ __device__ __forceinline__ uint64_t lv_count_le(const uint64_t (&pl)[8], uint32_
 // NC = counter planes above `fours` that the rounds can reach.  NB = the group's blocks when that is 1 or 2 (straight-line code
 // on the registers that came with the header), 0: a loop that requests block b + 2 while block b is counted (blk = this lane's
 // slab of block 2).
-typedef const uint64_t __attribute__((address_space(3))) sweep_lds_cu64;
-__device__ __forceinline__ uint64_t sweep_word_at(uint32_t a) { return *(sweep_lds_cu64*)(uintptr_t)a; }
-
-template <int NC>
-__device__ __forceinline__ void sweep_count_block(const uint32_t (&nb)[8], uint64_t own, uint64_t& ones, uint64_t& twos, uint64_t& fours,
-                                                  uint64_t (&c)[5]) {
-    uint64_t d[8];
+template <int NC, typename WT, typename PW>
+__device__ __forceinline__ void sweep_count_block(const uint32_t (&nb)[8], PW own, PW& ones, PW& twos, PW& fours, PW (&c)[5]) {
+    PW d[8];
 #pragma unroll
-    for (int q = 0; q < 8; ++q) d[q] = sweep_word_at(nb[q]) ^ own;   // padding = the node itself: 0
-    uint64_t twosA, twosB, foursA, foursB, carry;
-    csa(twosA, ones, ones, d[0], d[1]);
-    csa(twosB, ones, ones, d[2], d[3]);
-    csa(foursA, twos, twos, twosA, twosB);
-    csa(twosA, ones, ones, d[4], d[5]);
-    csa(twosB, ones, ones, d[6], d[7]);
-    csa(foursB, twos, twos, twosA, twosB);
-    csa(carry, fours, fours, foursA, foursB);
-#pragma unroll
-    for (int p = 0; p < NC; ++p) {
-        const uint64_t t = c[p] & carry;
-        c[p] ^= carry;
-        carry = t;
-    }
+    for (int q = 0; q < 8; ++q) d[q] = sweep_word_at<WT>(nb[q]) ^ own;   // padding = the node itself: 0
+    add8<NC>(d, ones, twos, fours, c);
 }
 
-template <int NB, int NC, int NP>
-__device__ __forceinline__ uint64_t sweep_group_flips(const int32_t* __restrict__ blk, int rounds, const uint32_t (&nb0)[8],
-                                                      const uint32_t (&nb1)[8], uint64_t own, uint32_t thr, uint32_t lcode) {
-    uint64_t ones = 0, twos = 0, fours = 0, c[5] = {0, 0, 0, 0, 0};
+template <int NB, int NC, int NP, typename WT, typename PW>
+__device__ __forceinline__ PW sweep_group_flips(const int32_t* __restrict__ blk, int rounds, const uint32_t (&nb0)[8],
+                                                const uint32_t (&nb1)[8], PW own, uint32_t thr, uint32_t lcode) {
+    PW ones = 0, twos = 0, fours = 0, c[5] = {0, 0, 0, 0, 0};
     if constexpr (NB == 1) {
-        sweep_count_block<NC>(nb0, own, ones, twos, fours, c);
+        sweep_count_block<NC, WT>(nb0, own, ones, twos, fours, c);
     } else if constexpr (NB == 2) {
-        sweep_count_block<NC>(nb0, own, ones, twos, fours, c);
-        sweep_count_block<NC>(nb1, own, ones, twos, fours, c);
+        sweep_count_block<NC, WT>(nb0, own, ones, twos, fours, c);
+        sweep_count_block<NC, WT>(nb1, own, ones, twos, fours, c);
     } else {
         uint32_t nb[8], nx[8];
 #pragma unroll
@@ -202,53 +193,71 @@ __device__ __forceinline__ uint64_t sweep_group_flips(const int32_t* __restrict_
                 na = *reinterpret_cast<const u32x4*>(blk);
                 nbv = *reinterpret_cast<const u32x4*>(blk + 256);
             }
-            sweep_count_block<NC>(nb, own, ones, twos, fours, c);
+            sweep_count_block<NC, WT>(nb, own, ones, twos, fours, c);
 #pragma unroll
             for (int q = 0; q < 8; ++q) nb[q] = nx[q];
             nx[0] = na.x; nx[1] = na.y; nx[2] = na.z; nx[3] = na.w;
             nx[4] = nbv.x; nx[5] = nbv.y; nx[6] = nbv.z; nx[7] = nbv.w;
         }
     }
+    // mask of envs whose vertical counter is <= thr (per lane): the carry chain of c + ~thr (rls_planes.h: lv_le_const)
     const int gl = __builtin_amdgcn_readlane((int)lcode, 0);
     if (gl > 0) {   // degrees < 256: the sum over a row's lanes stays below 2^8
-        uint64_t pv[8] = {ones, twos, fours, c[0], c[1], c[2], c[3], c[4]};
-        lv_merge_planes<1>(pv, 0ull - (uint64_t)(lcode >= 1u));
-        if (gl > 1) lv_merge_planes<2>(pv, 0ull - (uint64_t)(lcode >= 2u));
-        if (gl > 2) lv_merge_planes<4>(pv, 0ull - (uint64_t)(lcode >= 3u));
-        return lv_count_le<8>(pv, thr);
+        PW pv[8] = {ones, twos, fours, c[0], c[1], c[2], c[3], c[4]};
+        lv_merge_planes<1>(pv, (PW)0 - (PW)(lcode >= 1u));
+        if (gl > 1) lv_merge_planes<2>(pv, (PW)0 - (PW)(lcode >= 2u));
+        if (gl > 2) lv_merge_planes<4>(pv, (PW)0 - (PW)(lcode >= 3u));
+        return lv_le_const<8>(pv, thr);
     }
-    const uint64_t pl[8] = {ones, twos, fours, c[0], c[1], c[2], c[3], c[4]};
-    return lv_count_le<NP>(pl, thr);
+    const PW pl[8] = {ones, twos, fours, c[0], c[1], c[2], c[3], c[4]};
+    return lv_le_const<NP>(pl, thr);
 }
 
 // A hub (a row of 256 ... 4095 entries) is a group of its own with lane = neighbour: per-lane vertical counters over its
 // rounds (64 neighbours each; the first eight rounds arrive prefetched), every plane transposed across the wave and
-// popcounted -- lane e then holds env e's count -- and the same rule c <= deg / 2.
-__device__ __forceinline__ uint64_t sweep_hub_flips(const int32_t* __restrict__ ent, int rounds, const uint32_t (&nb0)[8], uint64_t own,
-                                                    uint32_t deg, int lane) {       // ent = the record's entries (behind its 64 header words)
-    uint64_t cv[7] = {0, 0, 0, 0, 0, 0, 0};                      // rounds <= 64
+// popcounted -- lane e then holds env e's count -- and the same rule c <= deg / 2.  64-bit planes: one plane per transpose.
+// 32-bit planes: two per transpose (lanes 0..31 get plane p of env lane, lanes 32..63 plane p + 1 of env lane - 32; the halves
+// are added), and only the lanes below the tile's env count vote.
+template <typename WT, typename PW>
+__device__ __forceinline__ PW sweep_hub_flips(const int32_t* __restrict__ ent, int rounds, const uint32_t (&nb0)[8], PW own,
+                                              uint32_t deg, int lane) {             // ent = the record's entries (behind its 64 header words)
+    constexpr int NPL = sizeof(PW) == 8 ? 7 : 8;                  // rounds <= 64: 7 planes (+ 1 to pair them)
+    PW cv[NPL] = {};
     auto add = [&](uint32_t off) {
-        uint64_t carry = sweep_word_at(off) ^ own;
+        PW carry = sweep_word_at<WT>(off) ^ own;
 #pragma unroll
-        for (int p = 0; p < 7; ++p) { const uint64_t t = cv[p] & carry; cv[p] ^= carry; carry = t; }
+        for (int p = 0; p < 7; ++p) { const PW t = cv[p] & carry; cv[p] ^= carry; carry = t; }
     };
 #pragma unroll
     for (int q = 0; q < 8; ++q) add(nb0[q]);
     for (int r = 8; r < rounds; ++r) add((uint32_t)ent[(r >> 3) * 512 + ((r >> 2) & 1) * 256 + lane * 4 + (r & 3)]);
     const BitXpose xc = bit_xpose_consts(lane);
     int cnt = 0;
+    if constexpr (sizeof(PW) == 8) {
 #pragma unroll
-    for (int p = 0; p < 7; ++p) {
-        uint32_t r0 = (uint32_t)cv[p], r1 = (uint32_t)(cv[p] >> 32);
-        bit_transpose64(r0, r1, xc);
-        cnt += (__builtin_popcount(r0) + __builtin_popcount(r1)) << p;
+        for (int p = 0; p < 7; ++p) {
+            uint32_t r0 = (uint32_t)cv[p], r1 = (uint32_t)(cv[p] >> 32);
+            bit_transpose64(r0, r1, xc);
+            cnt += (__builtin_popcount(r0) + __builtin_popcount(r1)) << p;
+        }
+        return ballot64((uint32_t)cnt <= (deg >> 1));
+    } else {
+        const int half = lane >> 5;
+#pragma unroll
+        for (int p = 0; p < 8; p += 2) {
+            uint32_t r0 = cv[p], r1 = cv[p + 1];
+            bit_transpose64(r0, r1, xc);
+            cnt += (__builtin_popcount(r0) + __builtin_popcount(r1)) << (p + half);
+        }
+        cnt += __shfl_xor(cnt, 32, 64);
+        return (uint32_t)ballot64(lane < 8 * (int)sizeof(WT) && (uint32_t)cnt <= (deg >> 1));
     }
-    return ballot64((uint32_t)cnt <= (deg >> 1));
 }
 
-template <int W>
-__device__ __forceinline__ void sweep_tile_levels(uint64_t* words, const int32_t* lvp, const int32_t* __restrict__ data,
+template <int W, typename WT>
+__device__ __forceinline__ void sweep_tile_levels(WT* words, const int32_t* lvp, const int32_t* __restrict__ data,
                                                   int64_t G, int64_t N, int lane, int w) {
+    typedef plane_word_t<WT> PW;
     constexpr uint32_t M = 0x3fffffffu;
     // table entries are used as LDS addresses: the tile must sit at LDS address 0 (every caller puts it first in its dynamic LDS
     // and has no static LDS)
@@ -294,21 +303,21 @@ __device__ __forceinline__ void sweep_tile_levels(uint64_t* words, const int32_t
         const int rounds = (int)((p1 - p0) >> 6) - 1;        // a multiple of 8
         if (((uint32_t)__builtin_amdgcn_readlane(chunk, (int)(k & 63)) >> 30) & 1u) {   // a hub: one node, lane = neighbour
             const uint32_t hnode = (uint32_t)__builtin_amdgcn_readlane((int)hdr, 0), hdeg = (uint32_t)__builtin_amdgcn_readlane((int)hdr, 1);
-            const uint64_t hown = words[hnode];
-            const uint64_t hflip = sweep_hub_flips(data + p0 + 64, rounds, nb0, hown, hdeg, lane);
-            if (lane == 0) words[hnode] = hown ^ hflip;
+            const PW hown = (PW)words[hnode];
+            const PW hflip = sweep_hub_flips<WT>(data + p0 + 64, rounds, nb0, hown, hdeg, lane);
+            if (lane == 0) words[hnode] = (WT)(hown ^ hflip);
             prefetch(k + W);
             continue;
         }
         const uint32_t node = hdr & 0xFFFFFu, thr = (hdr >> 20) & 0xFFu, lcode = (hdr >> 28) & 3u;
-        const uint64_t own = words[node];
+        const PW own = (PW)words[node];
         const int32_t* blk = data + p0 + 64 + 1024 + 4 * lane;      // this lane's slab of block 2
-        uint64_t flip;
-        if (rounds == 8) flip = sweep_group_flips<1, 1, 4>(blk, rounds, nb0, nb1, own, thr, lcode);
-        else if (rounds == 16) flip = sweep_group_flips<2, 2, 5>(blk, rounds, nb0, nb1, own, thr, lcode);
-        else if (rounds <= 24) flip = sweep_group_flips<0, 2, 5>(blk, rounds, nb0, nb1, own, thr, lcode);     // (0: isolated nodes; 24)
-        else flip = sweep_group_flips<0, 4, 7>(blk, rounds, nb0, nb1, own, thr, lcode);
-        if (node < (uint32_t)N && (lane & ((1 << lcode) - 1)) == 0) words[node] = own ^ flip;
+        PW flip;
+        if (rounds == 8) flip = sweep_group_flips<1, 1, 4, WT>(blk, rounds, nb0, nb1, own, thr, lcode);
+        else if (rounds == 16) flip = sweep_group_flips<2, 2, 5, WT>(blk, rounds, nb0, nb1, own, thr, lcode);
+        else if (rounds <= 24) flip = sweep_group_flips<0, 2, 5, WT>(blk, rounds, nb0, nb1, own, thr, lcode);     // (0: isolated nodes; 24)
+        else flip = sweep_group_flips<0, 4, 7, WT>(blk, rounds, nb0, nb1, own, thr, lcode);
+        if (node < (uint32_t)N && (lane & ((1 << lcode) - 1)) == 0) words[node] = (WT)(own ^ flip);
         prefetch(k + W);
     }
     for (; passed < num_levels; ++passed) __syncthreads();

@@ -8,6 +8,7 @@
 // spin.  N * 8 bytes of LDS per wave (16 KB for G22, 80 KB for N = 10^4).
 #pragma once
 #include "rls_common.h"
+#include "rls_planes.h"
 #include <cstdlib>
 
 namespace rls {
@@ -559,74 +560,7 @@ __device__ __forceinline__ void tile_store_bytes(uint8_t* __restrict__ x, int64_
     for (int64_t n = w; n < N; n += W) row[n] = (uint8_t)((w32[(n << 1) + half] >> sh) & 1u);
 }
 
-// ---- bit-sliced (vertical) counters: plane p holds bit p of 64 independent counts.
-// carry-save adder on 64 counters at once; gfx950's v_bitop3 does a 3-input majority / parity in one op
-__device__ __forceinline__ void csa(uint64_t& hi, uint64_t& lo, uint64_t a, uint64_t b, uint64_t c) {
-    const uint32_t a0 = (uint32_t)a, a1 = (uint32_t)(a >> 32), b0 = (uint32_t)b, b1 = (uint32_t)(b >> 32),
-                   c0 = (uint32_t)c, c1 = (uint32_t)(c >> 32);
-    const uint32_t h0 = __builtin_amdgcn_bitop3_b32(a0, b0, c0, 0xE8), h1 = __builtin_amdgcn_bitop3_b32(a1, b1, c1, 0xE8);
-    const uint32_t l0 = __builtin_amdgcn_bitop3_b32(a0, b0, c0, 0x96), l1 = __builtin_amdgcn_bitop3_b32(a1, b1, c1, 0x96);
-    hi = ((uint64_t)h1 << 32) | h0;
-    lo = ((uint64_t)l1 << 32) | l0;
-}
-
-// lane exchange of a 64-bit plane with lane ^ 1, ^ 2 (DPP quad_perm 0xB1 / 0x4E) or ^ 4 (ds_swizzle bit mode), no memory
-template <int X>
-__device__ __forceinline__ uint64_t lv_lane_xor(uint64_t v) {
-    uint32_t lo, hi;
-    if constexpr (X == 4) {
-        lo = (uint32_t)__builtin_amdgcn_ds_swizzle((int)(uint32_t)v, 0x101F);          // and 0x1F, or 0, xor 4
-        hi = (uint32_t)__builtin_amdgcn_ds_swizzle((int)(uint32_t)(v >> 32), 0x101F);
-    } else {
-        constexpr int CTRL = X == 1 ? 0xB1 : 0x4E;
-        lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, 0xF, 0xF, false);
-        hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), CTRL, 0xF, 0xF, false);
-    }
-    return ((uint64_t)hi << 32) | lo;
-}
-
-// pl[0..7] += lane ^ X's pl[0..7] where `take` is all-ones (bit-sliced ripple-carry add, counts <= 128 in total)
-template <int X>
-__device__ __forceinline__ void lv_merge_planes(uint64_t (&pl)[8], uint64_t take) {
-    uint64_t carry = 0;
-#pragma unroll
-    for (int p = 0; p < 8; ++p) csa(carry, pl[p], pl[p], lv_lane_xor<X>(pl[p]) & take, carry);
-}
-
-// Bit-sliced compare of 64 vertical counters (planes pl[0 .. NP), plane p = bit p of every count) with a per-LANE constant
-// thr < 2^NP:   c <= thr  <=>  c + (2^NP - 1 - thr) < 2^NP  <=>  adding ~thr (NP bits) to c carries nothing out of plane
-// NP - 1.  Only the carry chain is needed -- one 3-input majority (v_bitop3) per plane and half, one v_bfe_i32 per plane for
-// the constant's bit -- where the scan from the top plane down ("smaller so far / equal so far") took four operations per
-// plane and half.  Returns the mask of counters that are <= thr.
-template <int NP, int CAP>
-__device__ __forceinline__ uint64_t lv_le_const(const uint64_t (&pl)[CAP], uint32_t thr) {
-    static_assert(NP <= CAP, "planes");
-    const int nt = (int)~thr;
-    uint32_t c0 = 0, c1 = 0;
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        const uint32_t kb = (uint32_t)__builtin_amdgcn_sbfe(nt, p, 1);      // all ones where thr has bit p CLEAR
-        c0 = __builtin_amdgcn_bitop3_b32((uint32_t)pl[p], kb, c0, 0xE8);
-        c1 = __builtin_amdgcn_bitop3_b32((uint32_t)(pl[p] >> 32), kb, c1, 0xE8);
-    }
-    return ~(((uint64_t)c1 << 32) | c0);
-}
-
-// The same with one more plane below: mask of [2 c + low <= thr2], `low` a 0 | 1 bit per counter (a 64-bit word), thr2 < 2^(NP+1).
-template <int NP, int CAP>
-__device__ __forceinline__ uint64_t lv_le_const_x2(const uint64_t (&pl)[CAP], uint64_t low, uint32_t thr2) {
-    static_assert(NP <= CAP, "planes");
-    const int nt = (int)~thr2;
-    const uint32_t k0 = (uint32_t)__builtin_amdgcn_sbfe(nt, 0, 1);
-    uint32_t c0 = (uint32_t)low & k0, c1 = (uint32_t)(low >> 32) & k0;       // majority with carry-in 0
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        const uint32_t kb = (uint32_t)__builtin_amdgcn_sbfe(nt, p + 1, 1);
-        c0 = __builtin_amdgcn_bitop3_b32((uint32_t)pl[p], kb, c0, 0xE8);
-        c1 = __builtin_amdgcn_bitop3_b32((uint32_t)(pl[p] >> 32), kb, c1, 0xE8);
-    }
-    return ~(((uint64_t)c1 << 32) | c0);
-}
+// (the bit-sliced counters that run on a tile: rls_planes.h)
 
 __device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int mask) {
     uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);

@@ -1,22 +1,18 @@
 // The 32-env "half tile": words32[n] is a 32-bit word whose bit e is the spin of node n in env (b0 + e) -- N * 4 bytes of
 // LDS instead of N * 8, for graphs past the 64-env tile (20 224 < N <= ~40 000: rls_tile.h keeps one word per node in LDS) and
-// as twice as many, half as long workgroups where a launch has few tiles per CU.  Same building blocks as rls_tile.h: a wave
-// still turns 64 x 64 bits at a time -- lanes 0..31 hold the 32 envs' bytes of one 64-node block, lanes 32..63 the SAME envs'
-// bytes of the next block, so the transpose leaves lane p with (r0 = the 32 envs of node p in the first block, r1 = in the
-// second): two words32 per lane and transpose, nothing wasted.
+// as twice as many, half as long workgroups where a launch has few tiles per CU.  The loaders and stores use the building blocks of
+// rls_tile.h: a wave still turns 64 x 64 bits at a time -- lanes 0..31 hold the 32 envs' bytes of one 64-node block, lanes 32..63
+// the SAME envs' bytes of the next block, so the transpose leaves lane p with (r0 = the 32 envs of node p in the first block, r1 =
+// in the second): two words32 per lane and transpose, nothing wasted.
+// This file holds only what is about the tile's width: kHalf, narrow_tile and the byte <-> bit corner turns.  The cut counter
+// (rls_cutcount.h) and the level-parallel sweep (rls_sweep.h) take these tiles' words as they take 64-bit ones, on 32-bit planes
+// (rls_planes.h).
 #pragma once
 #include "rls_tile.h"
 
 namespace rls {
 
 constexpr int kHalf = 32;   // envs per half tile
-
-// carry-save adder on 32 counters at once
-__device__ __forceinline__ void csa32(uint32_t& hi, uint32_t& lo, uint32_t a, uint32_t b, uint32_t c) {
-    const uint32_t h = __builtin_amdgcn_bitop3_b32(a, b, c, 0xE8), l = __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
-    hi = h;
-    lo = l;
-}
 
 // Load the half tile of envs [b0, b0 + 32) x nodes [0, N) into words32[0..N).  W waves share the job (wave w takes every W-th
 // 128-node chunk); callers sync afterwards.  `stage` = this wave's kStageBytes of LDS (16-byte aligned) or nullptr.
@@ -314,273 +310,6 @@ __device__ __forceinline__ void tilen_store_bytes(uint8_t* __restrict__ x, int64
     }
     if (!valid || blk != 0) return;
     for (int64_t n = w; n < N; n += W) row[n] = (uint8_t)(((uint32_t)words[n] >> env) & 1u);
-}
-
-// K1 core on a half tile: every lane takes every 64th stored edge, XORs the two 32-env words and feeds a bit-sliced
-// Harley-Seal counter (rls_cutcount.h on 32-bit planes); the 64 lanes' counts are summed by transposing two planes at a time
-// across the wave (lanes 0..31 receive plane p of env lane, lanes 32..63 plane p + 1 of env lane - 32) and popcounting.
-// Returns, in lanes 0..31, wave w's partial count for env b0 + lane (lanes 32..63: 0).
-// (WT: the LDS word -- uint32_t for the half tile, uint16_t / uint8_t for the narrow tiles below, whose planes simply leave the upper
-// bits of the 32-bit registers zero: lanes beyond the tile's envs end with a count of 0)
-template <int P, typename WT = uint32_t>
-__device__ __forceinline__ int64_t tile32_cut_count(const WT* __restrict__ words32, const int32_t* __restrict__ eu,
-                                                    const int32_t* __restrict__ ev, int64_t E, int lane, int w, int W) {
-    constexpr int PL = (P - 5) < 5 ? 5 : (P - 5);           // per-lane count <= ceil(E / 64) < 2^(P - 5)
-    constexpr int PLE = (PL + 1) & ~1;
-    uint32_t ones = 0, twos = 0, fours = 0, eights = 0, c[PLE];
-#pragma unroll
-    for (int p = 0; p < PLE; ++p) c[p] = 0;
-    auto eight = [&](const uint32_t (&d)[8]) -> uint32_t {
-        uint32_t twosA, twosB, foursA, foursB, e8;
-        csa32(twosA, ones, ones, d[0], d[1]);
-        csa32(twosB, ones, ones, d[2], d[3]);
-        csa32(foursA, twos, twos, twosA, twosB);
-        csa32(twosA, ones, ones, d[4], d[5]);
-        csa32(twosB, ones, ones, d[6], d[7]);
-        csa32(foursB, twos, twos, twosA, twosB);
-        csa32(e8, fours, fours, foursA, foursB);
-        return e8;
-    };
-    auto block16 = [&](const uint32_t (&dA)[8], const uint32_t (&dB)[8]) {
-        const uint32_t eA = eight(dA), eB = eight(dB);
-        uint32_t carry;
-        csa32(carry, eights, eights, eA, eB);
-#pragma unroll
-        for (int p = 4; p < PL; ++p) {
-            const uint32_t t = c[p] & carry;
-            c[p] ^= carry;
-            carry = t;
-        }
-    };
-    constexpr int64_t BLK = 16 * kWave;
-    const int64_t nfull = E / BLK;
-    for (int64_t blk = w; blk < nfull; blk += W) {
-        const int32_t* pu = eu + blk * BLK + lane;
-        const int32_t* pv = ev + blk * BLK + lane;
-        int u[16], v[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) { u[k] = pu[k * kWave]; v[k] = pv[k * kWave]; }
-        uint32_t dA[8], dB[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) dA[k] = (uint32_t)words32[u[k]] ^ (uint32_t)words32[v[k]];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) dB[k] = (uint32_t)words32[u[8 + k]] ^ (uint32_t)words32[v[8 + k]];
-        block16(dA, dB);
-    }
-    if (nfull * BLK < E && (nfull % W) == w) {   // the ragged last block: clamped, unconditional loads, masked afterwards
-        int u[16], v[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const int64_t e = nfull * BLK + k * kWave + lane;
-            const int64_t ec = e < E ? e : E - 1;
-            u[k] = eu[ec];
-            v[k] = ev[ec];
-        }
-        uint32_t dA[8], dB[8];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const int64_t e = nfull * BLK + k * kWave + lane;
-            const uint32_t d = (e < E) ? ((uint32_t)words32[u[k]] ^ (uint32_t)words32[v[k]]) : 0u;
-            if (k < 8) dA[k] = d; else dB[k - 8] = d;
-        }
-        block16(dA, dB);
-    }
-    c[0] = ones; c[1] = twos; c[2] = fours; c[3] = eights;
-    const BitXpose xc = bit_xpose_consts(lane);
-    const int half = lane >> 5;
-    int64_t total = 0;
-#pragma unroll
-    for (int p = 0; p < PLE; p += 2) {
-        // row l = (c[p + 1] : c[p]) of lane l; column q < 32 = bit q of plane p over the 64 lanes, column 32 + q = of plane p + 1
-        uint32_t r0 = c[p], r1 = c[p + 1];
-        bit_transpose64(r0, r1, xc);
-        const int cnt = __builtin_popcount(r0) + __builtin_popcount(r1);
-        // this lane holds column xc.node-independent index = lane itself (plain 64 x 64 transpose: no pack_bits permutation here)
-        total += (int64_t)cnt << (p + half);
-    }
-    // lane q (< 32) has the even planes of env q, lane 32 + q the odd ones: add the two
-    const int64_t other = shfl_xor64((uint64_t)total, 32);
-    return half == 0 ? total + other : 0;
-}
-
-// ---- the level-parallel sweep (rls_sweep.h: sweep_tile_levels) on half-tile words.  The SAME schedule: its entries are byte
-// offsets of 64-bit words (node * 8), halved here; a group costs the same instructions per plane and HALF as many planes' halves.
-template <int X>
-__device__ __forceinline__ uint32_t lv32_lane_xor(uint32_t v) {
-    if constexpr (X == 4) return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x101F);
-    else return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, X == 1 ? 0xB1 : 0x4E, 0xF, 0xF, false);
-}
-template <int X>
-__device__ __forceinline__ void lv32_merge_planes(uint32_t (&pl)[8], uint32_t take) {
-    uint32_t carry = 0;
-#pragma unroll
-    for (int p = 0; p < 8; ++p) csa32(carry, pl[p], pl[p], lv32_lane_xor<X>(pl[p]) & take, carry);
-}
-template <int NP>
-__device__ __forceinline__ uint32_t lv32_le_const(const uint32_t (&pl)[8], uint32_t thr) {   // rls_tile.h: lv_le_const
-    const int nt = (int)~thr;
-    uint32_t c0 = 0;
-#pragma unroll
-    for (int p = 0; p < NP; ++p) c0 = __builtin_amdgcn_bitop3_b32(pl[p], (uint32_t)__builtin_amdgcn_sbfe(nt, p, 1), c0, 0xE8);
-    return ~c0;
-}
-
-// the tile word of the node whose 64-bit-word byte offset is `nb` (the schedule's entries): the tile sits at LDS address 0
-template <typename WT>
-__device__ __forceinline__ uint32_t sweep32_word_at(uint32_t nb) {
-    typedef const WT __attribute__((address_space(3))) lds_cwt;
-    constexpr int SH = sizeof(WT) == 4 ? 1 : (sizeof(WT) == 2 ? 2 : 3);
-    return (uint32_t)*(lds_cwt*)(uintptr_t)(nb >> SH);
-}
-
-template <int NC, typename WT>
-__device__ __forceinline__ void sweep32_count_block(const uint32_t (&nb)[8], uint32_t own, uint32_t& ones, uint32_t& twos, uint32_t& fours,
-                                                    uint32_t (&c)[5]) {
-    uint32_t d[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) d[q] = sweep32_word_at<WT>(nb[q]) ^ own;   // padding = the node itself: 0
-    uint32_t twosA, twosB, foursA, foursB, carry;
-    csa32(twosA, ones, ones, d[0], d[1]);
-    csa32(twosB, ones, ones, d[2], d[3]);
-    csa32(foursA, twos, twos, twosA, twosB);
-    csa32(twosA, ones, ones, d[4], d[5]);
-    csa32(twosB, ones, ones, d[6], d[7]);
-    csa32(foursB, twos, twos, twosA, twosB);
-    csa32(carry, fours, fours, foursA, foursB);
-#pragma unroll
-    for (int p = 0; p < NC; ++p) {
-        const uint32_t t = c[p] & carry;
-        c[p] ^= carry;
-        carry = t;
-    }
-}
-
-// (rls_sweep.h: sweep_group_flips -- NB = the group's blocks when 1 or 2, 0 = the loop; blk = this lane's slab of block 2)
-template <int NB, int NC, int NP, typename WT>
-__device__ __forceinline__ uint32_t sweep32_group_flips(const int32_t* __restrict__ blk, int rounds, const uint32_t (&nb0)[8],
-                                                        const uint32_t (&nb1)[8], uint32_t own, uint32_t thr, uint32_t lcode) {
-    uint32_t ones = 0, twos = 0, fours = 0, c[5] = {0, 0, 0, 0, 0};
-    if constexpr (NB == 1) {
-        sweep32_count_block<NC, WT>(nb0, own, ones, twos, fours, c);
-    } else if constexpr (NB == 2) {
-        sweep32_count_block<NC, WT>(nb0, own, ones, twos, fours, c);
-        sweep32_count_block<NC, WT>(nb1, own, ones, twos, fours, c);
-    } else {
-        uint32_t nb[8], nx[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) { nb[q] = nb0[q]; nx[q] = nb1[q]; }
-        for (int r0 = 0; r0 < rounds; r0 += 8, blk += 512) {
-            u32x4 na, nbv;
-            if (r0 + 16 < rounds) {
-                na = *reinterpret_cast<const u32x4*>(blk);
-                nbv = *reinterpret_cast<const u32x4*>(blk + 256);
-            }
-            sweep32_count_block<NC, WT>(nb, own, ones, twos, fours, c);
-#pragma unroll
-            for (int q = 0; q < 8; ++q) nb[q] = nx[q];
-            nx[0] = na.x; nx[1] = na.y; nx[2] = na.z; nx[3] = na.w;
-            nx[4] = nbv.x; nx[5] = nbv.y; nx[6] = nbv.z; nx[7] = nbv.w;
-        }
-    }
-    const int gl = __builtin_amdgcn_readlane((int)lcode, 0);
-    if (gl > 0) {
-        uint32_t pv[8] = {ones, twos, fours, c[0], c[1], c[2], c[3], c[4]};
-        lv32_merge_planes<1>(pv, 0u - (uint32_t)(lcode >= 1u));
-        if (gl > 1) lv32_merge_planes<2>(pv, 0u - (uint32_t)(lcode >= 2u));
-        if (gl > 2) lv32_merge_planes<4>(pv, 0u - (uint32_t)(lcode >= 3u));
-        return lv32_le_const<8>(pv, thr);
-    }
-    const uint32_t pl[8] = {ones, twos, fours, c[0], c[1], c[2], c[3], c[4]};
-    return lv32_le_const<NP>(pl, thr);
-}
-
-// a hub: lane = neighbour, per-lane counters over its rounds, every plane transposed across the wave and popcounted (two planes
-// per transpose: lanes 0..31 get plane p of env lane, lanes 32..63 plane p + 1 of env lane - 32)
-template <typename WT>
-__device__ __forceinline__ uint32_t sweep32_hub_flips(const int32_t* __restrict__ ent, int rounds, const uint32_t (&nb0)[8], uint32_t own,
-                                                      uint32_t deg, int lane) {     // ent = the record's entries (behind its 64 header words)
-    uint32_t cv[8] = {0, 0, 0, 0, 0, 0, 0, 0};                      // rounds <= 64: 7 planes (+ 1 to pair them)
-    auto add = [&](uint32_t off) {
-        uint32_t carry = sweep32_word_at<WT>(off) ^ own;
-#pragma unroll
-        for (int p = 0; p < 7; ++p) { const uint32_t t = cv[p] & carry; cv[p] ^= carry; carry = t; }
-    };
-#pragma unroll
-    for (int q = 0; q < 8; ++q) add(nb0[q]);
-    for (int r = 8; r < rounds; ++r) add((uint32_t)ent[(r >> 3) * 512 + ((r >> 2) & 1) * 256 + lane * 4 + (r & 3)]);
-    const BitXpose xc = bit_xpose_consts(lane);
-    const int half = lane >> 5;
-    int cnt = 0;
-#pragma unroll
-    for (int p = 0; p < 8; p += 2) {
-        uint32_t r0 = cv[p], r1 = cv[p + 1];
-        bit_transpose64(r0, r1, xc);
-        cnt += (__builtin_popcount(r0) + __builtin_popcount(r1)) << (p + half);
-    }
-    cnt += __shfl_xor(cnt, 32, 64);
-    return (uint32_t)ballot64(lane < 8 * (int)sizeof(WT) && (uint32_t)cnt <= (deg >> 1));
-}
-
-template <int W, typename WT = uint32_t>
-__device__ __forceinline__ void sweep32_tile_levels(WT* words32, const int32_t* lvp, const int32_t* __restrict__ data, int64_t G,
-                                                    int64_t N, int lane, int w) {
-    constexpr uint32_t M = 0x3fffffffu;
-    if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)words32 != 0u) __builtin_trap();   // entries are LDS addresses (rls_sweep.h)
-    uint32_t hdr = (uint32_t)N;
-    uint32_t nb0[8], nb1[8];
-    auto prefetch = [&](int64_t k) {
-        if (k < G) {
-            const int32_t* rec = data + ((uint32_t)lvp[k] & M);
-            hdr = (uint32_t)rec[lane];
-            const u32x4 a = *reinterpret_cast<const u32x4*>(rec + 64 + 4 * lane), b = *reinterpret_cast<const u32x4*>(rec + 320 + 4 * lane);
-            const u32x4 c = *reinterpret_cast<const u32x4*>(rec + 576 + 4 * lane), d = *reinterpret_cast<const u32x4*>(rec + 832 + 4 * lane);
-            nb0[0] = a.x; nb0[1] = a.y; nb0[2] = a.z; nb0[3] = a.w; nb0[4] = b.x; nb0[5] = b.y; nb0[6] = b.z; nb0[7] = b.w;
-            nb1[0] = c.x; nb1[1] = c.y; nb1[2] = c.z; nb1[3] = c.w; nb1[4] = d.x; nb1[5] = d.y; nb1[6] = d.z; nb1[7] = d.w;
-        }
-    };
-    prefetch(w);
-    int num_levels = 0;
-    for (int64_t k0 = 0; k0 < G; k0 += kWave)
-        num_levels += __builtin_popcountll(ballot64(k0 + lane < G && (lvp[k0 + lane < G ? k0 + lane : G] >> 31) != 0));
-    int chunk = 0, chunk_next = 0;
-    int64_t cbase = -1;
-    uint64_t lmask = 0;
-    int lev_base = 0, passed = 0;
-    for (int64_t k = w; k < G; k += W) {
-        if ((k & ~(int64_t)63) != cbase) {
-            cbase = k & ~(int64_t)63;
-            lev_base += __builtin_popcountll(lmask);
-            const int64_t a0 = cbase + lane <= G ? cbase + lane : G, a1 = cbase + 1 + lane <= G ? cbase + 1 + lane : G;
-            chunk = lvp[a0];
-            chunk_next = lvp[a1];
-            lmask = ballot64(cbase + lane < G && (chunk >> 31) != 0);
-        }
-        const int need = lev_base + __builtin_popcountll(lmask & ((2ull << (k & 63)) - 1ull));
-        for (; passed < need; ++passed) __syncthreads();
-        const int64_t p0 = (uint32_t)__builtin_amdgcn_readlane(chunk, (int)(k & 63)) & M;
-        const int64_t p1 = (uint32_t)__builtin_amdgcn_readlane(chunk_next, (int)(k & 63)) & M;
-        const int rounds = (int)((p1 - p0) >> 6) - 1;
-        if (((uint32_t)__builtin_amdgcn_readlane(chunk, (int)(k & 63)) >> 30) & 1u) {
-            const uint32_t hnode = (uint32_t)__builtin_amdgcn_readlane((int)hdr, 0), hdeg = (uint32_t)__builtin_amdgcn_readlane((int)hdr, 1);
-            const uint32_t hown = (uint32_t)words32[hnode];
-            const uint32_t hflip = sweep32_hub_flips<WT>(data + p0 + 64, rounds, nb0, hown, hdeg, lane);
-            if (lane == 0) words32[hnode] = (WT)(hown ^ hflip);
-            prefetch(k + W);
-            continue;
-        }
-        const uint32_t node = hdr & 0xFFFFFu, thr = (hdr >> 20) & 0xFFu, lcode = (hdr >> 28) & 3u;
-        const uint32_t own = (uint32_t)words32[node];
-        const int32_t* blk = data + p0 + 64 + 1024 + 4 * lane;      // this lane's slab of block 2
-        uint32_t flip;
-        if (rounds == 8) flip = sweep32_group_flips<1, 1, 4, WT>(blk, rounds, nb0, nb1, own, thr, lcode);
-        else if (rounds == 16) flip = sweep32_group_flips<2, 2, 5, WT>(blk, rounds, nb0, nb1, own, thr, lcode);
-        else if (rounds <= 24) flip = sweep32_group_flips<0, 2, 5, WT>(blk, rounds, nb0, nb1, own, thr, lcode);
-        else flip = sweep32_group_flips<0, 4, 7, WT>(blk, rounds, nb0, nb1, own, thr, lcode);
-        if (node < (uint32_t)N && (lane & ((1 << lcode) - 1)) == 0) words32[node] = (WT)(own ^ flip);
-        prefetch(k + W);
-    }
-    for (; passed < num_levels; ++passed) __syncthreads();
-    __syncthreads();
 }
 
 }  // namespace rls

@@ -1,4 +1,4 @@
-"""The bit-sliced cut counter (csrc/rls_cutcount.h: tile_cut_count<P>, csrc/rls_tile32.h: tile32_cut_count<P, WT>) under every kernel that
+"""The bit-sliced cut counter (csrc/rls_cutcount.h: tile_cut_count<P> on 64-bit words and on the half / narrow tiles' words) under every kernel that
 reports an objective with it, at each plane count P, on both sides of each plane limit, at the edges of its 1024-edge blocks, and on
 the one state that fills its top plane.
 
